@@ -9,8 +9,15 @@ smallest witnesses are reduced in registers and flushed by atomics.  With N rank
 (weak scaling) and the only exchange is one all-reduce (MIN of witness index, SUM of counts) of
 2 x 8 B per tape over RCCL.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--dump-outputs DIR`
+also writes what the last timed step returned to its caller (per-tape first witness and hit count)
+as DIR/first_hit.npy and DIR/hit_count.npy; tapes and assignments are seeded, so two builds run
+with the same arguments can be compared array for array.  `--full` adds everything else the
+benchmark measures, each after the timed region: the full-evaluation companion step, the roofline
+block (profile lookups and the VALU issue microbenchmark) and the CPU baseline.
 
 `--gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset) starts the second form itself,
 as a child process before anything touches the GPU, and exits with its return code; rank 0's
@@ -51,6 +58,15 @@ def cpu_baseline(ts, seed, seconds: float):
     one = ctape.benchmark(ts, seed, seconds / 2, threads=1)
     out["single_core"] = {"value": one["value"], "cores": 1, "sample": one["sample"]}
     return out
+
+
+def dump_outputs(path: str, fh, hc) -> None:
+    """--dump-outputs: the two arrays the timed path hands its caller after the last timed step,
+    per tape: first_hit (smallest witness index, -1 where no row satisfies the tape) and hit_count.
+    Both are below 2^53, so float64 holds them exactly."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "first_hit.npy"), fh.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "hit_count.npy"), hc.cpu().numpy().astype(np.float64))
 
 
 def launch_ranks(argv, n: int) -> int:
@@ -110,21 +126,34 @@ def main() -> None:
     ap.add_argument("--full-eval", action="store_true",
                     help="jit: evaluate every conjunct of every row (MH_JIT_FULL_EVAL) instead of "
                          "leaving a tape once no row of the wave can satisfy it; same results")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: "
+                         "the full-evaluation companion step, the roofline block (profile "
+                         "lookups, VALU issue microbenchmark) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the per-tape results of the last timed step to DIR/first_hit.npy "
+                         "and DIR/hit_count.npy (float64)")
     ap.add_argument("--no-companion", action="store_true",
-                    help="skip the full-evaluation companion step (N=1, jit, short-circuit runs "
-                         "time one full-evaluation step after the timed region and check that "
-                         "its per-tape results are identical)")
+                    help="with --full: skip the full-evaluation companion step (N=1, jit, "
+                         "short-circuit runs time one full-evaluation step after the timed "
+                         "region and check that its per-tape results are identical)")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: --rows-per-gpu is the TOTAL row count (config 5: "
                          "2^26 in total) split over the ranks, instead of every rank sweeping "
                          "that many (weak scaling, the default)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="with --full: time budget of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--launch-check", action="store_true",
                     help="check the rank launch only (gloo, no GPU): one JSON line with the ranks")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(sys.argv[1:], args.gpus))
     if args.launch_check:
@@ -231,7 +260,68 @@ def main() -> None:
         if world > 1:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:  # before the companion step reuses the result buffers
+        dump_outputs(args.dump_outputs, fh, hc)
     short_circuit = args.engine == "jit" and not args.full_eval
+    line = {
+        "metric": "constraint-evals/sec",
+        "value": value,
+        "unit": "evals/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic (seeded config-5 tapes, counter-based PRNG assignments)",
+        "config": {
+            "workload": "synthetic config 5%s: %d random 256-bit constraint tapes x %d "
+                        "assignments per GPU, throughput mode"
+                        % (" (keccak variant: + one keccak256 of 512 bits per tape)"
+                           if args.variant == "keccak" else "", n_tapes, rows),
+            "variant": args.variant,
+            "tapes": n_tapes,
+            "rows_per_gpu": rows,
+            "rows_total": args.rows_per_gpu if args.strong else rows * world,
+            "vars": ts.n_vars,
+            "mode": "count_all",
+            "engine": args.engine,
+            "short_circuit": short_circuit,
+            "parallelism": "dp%d (row shards, all-reduce of per-tape results%s)"
+                           % (world, "" if exchange is None else ", %s RCCL" % exchange),
+        },
+        "exchange": exchange,
+        "exchange_fallback": "; ".join(exchange_fallback) or None,
+        "per_gpu": value / world,
+        "kernel_ms": kms,
+        "tapes_with_witness": hits,
+        "build": build_id,
+        "jit": jit_info,
+        "full": args.full,
+    }
+    if args.full:
+        full_figures(args, line, ctx, ct, ts, spec, assign, fh, hc, dev, index_base, rows,
+                     world, seed)
+    print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_figures(args, line, ctx, ct, ts, spec, assign, fh, hc, dev, index_base, rows, world,
+                 seed) -> None:
+    """--full: what the benchmark measures beside its headline figure, after the timed region --
+    the full-evaluation companion step, the roofline block and the CPU baseline -- added to
+    `line`."""
+    import torch
+
+    from mythril_amd import native
+
+    n_tapes = len(ts.tapes)
+    kms = line["kernel_ms"]
+    build_id = line["build"]
+    short_circuit = line["config"]["short_circuit"]
     companion = None
     if short_circuit and world == 1 and not args.no_companion:
         # the same step on native code without the short circuit: rate and identical results
@@ -307,80 +397,43 @@ def main() -> None:
         if alg:
             companion["roofline_frac_codegen"] = alg_per_eval * n_tapes * rows / (
                 companion["kernel_ms"] / 1e3) / 1e12 / NOMINAL_PEAK_TOPS
-    line = {
-        "metric": "constraint-evals/sec",
-        "value": value,
-        "unit": "evals/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong" if args.strong else "weak",
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic (seeded config-5 tapes, counter-based PRNG assignments)",
-        "config": {
-            "workload": "synthetic config 5%s: %d random 256-bit constraint tapes x %d "
-                        "assignments per GPU, throughput mode"
-                        % (" (keccak variant: + one keccak256 of 512 bits per tape)"
-                           if args.variant == "keccak" else "", n_tapes, rows),
-            "variant": args.variant,
-            "tapes": n_tapes,
-            "rows_per_gpu": rows,
-            "rows_total": args.rows_per_gpu if args.strong else rows * world,
-            "vars": ts.n_vars,
-            "mode": "count_all",
-            "engine": args.engine,
-            "short_circuit": short_circuit,
-            "parallelism": "dp%d (row shards, all-reduce of per-tape results%s)"
-                           % (world, "" if exchange is None else ", %s RCCL" % exchange),
-        },
-        "exchange": exchange,
-        "exchange_fallback": "; ".join(exchange_fallback) or None,
-        "per_gpu": value / world,
-        "kernel_ms": kms,
-        "tapes_with_witness": hits,
-        "build": build_id,
-        "jit": jit_info,
-        "roofline": {
-            "bound": "valu",
-            "achieved": min_rate,
-            "peak": NOMINAL_PEAK_TOPS,
-            "unit": "T u32-ops/s",
-            "frac": (min_rate / NOMINAL_PEAK_TOPS) if min_rate else None,
-            "min_lane_ops_per_eval": min_per_eval,
-            "min_profile": ("profiles/min_work.json (%d tapes x %d rows, code-independent op "
-                            "table)" % (mw["tapes_sampled"], mw["rows"])) if mw else None,
-            "achieved_codegen": alg_rate,
-            "frac_codegen": (alg_rate / NOMINAL_PEAK_TOPS) if alg_rate else None,
-            "traffic": traffic,
-            "traffic_unit": "bytes per launch (PMC FETCH_SIZE + WRITE_SIZE, profiles/)",
-            "alg_lane_ops_per_eval": alg_per_eval,
-            "alg_profile": ("profiles/alg_work.json build %s (%d tapes x %d rows)"
-                            % (build_id, alg["tapes_sampled"], alg["rows"])) if alg else None,
-            "executed": exec_rate,
-            "frac_executed": (exec_rate / NOMINAL_PEAK_TOPS) if exec_rate else None,
-            "exec_lane_ops_per_eval": (exec_ops / (n_tapes * rows)) if exec_ops else None,
-            "pmc_profile": pmc_tag,
-            "valu_busy_pmc": valu_busy,
-            "peak_measured_add_chain": peak_measured,
-            "optable_ops_per_eval": optable_per_row / n_tapes,
-            "note": "achieved = the code-independent minimum work per launch / this run's "
-                    "kernel time: per (tape, row) the cheapest node set deciding the row's Bool "
-                    "(lazy AND / OR / ITE, constants folded, demanded limbs) priced by a fixed "
-                    "per-op table of minimum u32 lane-ops (min_lane_ops_per_eval, "
-                    "scripts/min_work.py). achieved_codegen / frac_codegen = the same per "
-                    "(tape, row) prefix in the emitted conjunct order at THIS code's per-op "
-                    "cost (alg_lane_ops_per_eval, per build, scripts/alg_work.py on the host "
-                    "emulator of the emitted code). Both <= executed, so frac <= frac_codegen "
-                    "<= frac_executed <= 1. executed = PMC SQ_INSTS_VALU x 64 of the profile of "
-                    "this build (pmc_profile; null when none) / kernel time; frac_executed / "
-                    "frac = the lanes a wave keeps busy for rows already decided. peak = 256 CU "
-                    "x 4 SIMD x 32 lanes x 2.4 GHz (a wave64 VALU op issues over 2 cycles). "
-                    "optable_ops_per_eval prices SURVEY 8d's op table, which the native code "
-                    "undercuts (DESIGN 5.1): informational, not a work count.",
-        },
+    line["roofline"] = {
+        "bound": "valu",
+        "achieved": min_rate,
+        "peak": NOMINAL_PEAK_TOPS,
+        "unit": "T u32-ops/s",
+        "frac": (min_rate / NOMINAL_PEAK_TOPS) if min_rate else None,
+        "min_lane_ops_per_eval": min_per_eval,
+        "min_profile": ("profiles/min_work.json (%d tapes x %d rows, code-independent op "
+                        "table)" % (mw["tapes_sampled"], mw["rows"])) if mw else None,
+        "achieved_codegen": alg_rate,
+        "frac_codegen": (alg_rate / NOMINAL_PEAK_TOPS) if alg_rate else None,
+        "traffic": traffic,
+        "traffic_unit": "bytes per launch (PMC FETCH_SIZE + WRITE_SIZE, profiles/)",
+        "alg_lane_ops_per_eval": alg_per_eval,
+        "alg_profile": ("profiles/alg_work.json build %s (%d tapes x %d rows)"
+                        % (build_id, alg["tapes_sampled"], alg["rows"])) if alg else None,
+        "executed": exec_rate,
+        "frac_executed": (exec_rate / NOMINAL_PEAK_TOPS) if exec_rate else None,
+        "exec_lane_ops_per_eval": (exec_ops / (n_tapes * rows)) if exec_ops else None,
+        "pmc_profile": pmc_tag,
+        "valu_busy_pmc": valu_busy,
+        "peak_measured_add_chain": peak_measured,
+        "optable_ops_per_eval": sum(int(i["alg_ops"]) for i in ct.info()) / n_tapes,
+        "note": "achieved = the code-independent minimum work per launch / this run's "
+                "kernel time: per (tape, row) the cheapest node set deciding the row's Bool "
+                "(lazy AND / OR / ITE, constants folded, demanded limbs) priced by a fixed "
+                "per-op table of minimum u32 lane-ops (min_lane_ops_per_eval, "
+                "scripts/min_work.py). achieved_codegen / frac_codegen = the same per "
+                "(tape, row) prefix in the emitted conjunct order at THIS code's per-op "
+                "cost (alg_lane_ops_per_eval, per build, scripts/alg_work.py on the host "
+                "emulator of the emitted code). Both <= executed, so frac <= frac_codegen "
+                "<= frac_executed <= 1. executed = PMC SQ_INSTS_VALU x 64 of the profile of "
+                "this build (pmc_profile; null when none) / kernel time; frac_executed / "
+                "frac = the lanes a wave keeps busy for rows already decided. peak = 256 CU "
+                "x 4 SIMD x 32 lanes x 2.4 GHz (a wave64 VALU op issues over 2 cycles). "
+                "optable_ops_per_eval prices SURVEY 8d's op table, which the native code "
+                "undercuts (DESIGN 5.1): informational, not a work count.",
     }
     if companion is not None:
         line["full_eval"] = companion
@@ -390,9 +443,6 @@ def main() -> None:
         except Exception as e:  # pragma: no cover
             log("cpu baseline failed: %s" % e)
             line["cpu_baseline"] = None
-    print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -80,7 +80,7 @@ for step in "$@"; do
     noasm)    timeout -k 10 400 $PYT -m gpu tests/test_gpu_parity.py -k cpp_step_build > "$OUT/pytest_noasm.txt" 2>&1 ;;
     gpu)      timeout -k 10 1100 $PYT -m gpu tests > "$OUT/pytest_gpu.txt" 2>&1 ;;
     smoke)    timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.txt" 2>&1 ;;
-    bench)    timeout -k 10 600 python -u bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.log" ;;
+    bench)    timeout -k 10 600 python -u bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.log" ;;
     miss)     timeout -k 10 400 python -u scripts/miss_cost.py 5 > "$OUT/miss_cost.jsonl" 2> "$OUT/miss_cost.log" ;;
     queries)  timeout -k 10 400 python -u scripts/sieve_queries.py > "$OUT/sieve_queries.jsonl" 2> "$OUT/sieve_queries.log" ;;
     latency)  SIEVE_QUERY_REPS=9 timeout -k 10 300 python -u scripts/sieve_queries.py \
@@ -90,7 +90,7 @@ for step in "$@"; do
     interp)   MH_INTERP_SC=0 timeout -k 10 300 python -u scripts/interp_op_cost.py > "$OUT/interp_op_cost.jsonl" 2> "$OUT/interp_op_cost.log" ;;
     counters) timeout -k 10 120 rocprofv3 -L > "$OUT/counters.txt" 2>&1 ;;
     profile)  bash scripts/profile.sh "$TAG" ;;
-    kbench)   timeout -k 10 400 python -u bench.py --variant keccak --cpu-seconds 5 > "$OUT/bench_keccak.json" 2> "$OUT/bench_keccak.log" ;;
+    kbench)   timeout -k 10 400 python -u bench.py --full --variant keccak --cpu-seconds 5 > "$OUT/bench_keccak.json" 2> "$OUT/bench_keccak.log" ;;
     kprofile) bash scripts/profile.sh "${TAG}_keccak" --variant keccak ;;
     paths)    timeout -k 10 600 python -u scripts/path_scaling.py > "$OUT/path_scaling.jsonl" 2> "$OUT/path_scaling.log" ;;
     bfs)      timeout -k 10 600 python -u scripts/bfs_order.py --solve > "$OUT/bfs_order_solve.jsonl" 2> "$OUT/bfs_order_solve.log" && \
@@ -98,7 +98,7 @@ for step in "$@"; do
     jumpi)    timeout -k 10 600 python -u scripts/jumpi_order.py > "$OUT/jumpi_order.jsonl" 2> "$OUT/jumpi_order.log" ;;
     import)   timeout -k 10 300 python -u scripts/import_cost.py > "$OUT/import_cost.jsonl" 2> "$OUT/import_cost.log" ;;
     ibench)   timeout -k 10 600 python -u bench.py --engine interp --steps 1 --warmup 1 --no-companion --no-cpu-baseline > "$OUT/bench_interp.json" 2> "$OUT/bench_interp.log" ;;
-    strong)   timeout -k 10 400 python -u bench.py --strong --no-companion --cpu-seconds 3 > "$OUT/bench_strong.json" 2> "$OUT/bench_strong.log" ;;
+    strong)   timeout -k 10 400 python -u bench.py --full --strong --no-companion --cpu-seconds 3 > "$OUT/bench_strong.json" 2> "$OUT/bench_strong.log" ;;
     pylatency) SIEVE_HOST=python SIEVE_QUERY_REPS=9 timeout -k 10 300 python -u scripts/sieve_queries.py \
                 > "$OUT/sieve_queries_py_a.jsonl" 2> "$OUT/py_a.log" && \
               SIEVE_HOST=python SIEVE_QUERY_REPS=9 timeout -k 10 300 python -u scripts/sieve_queries.py \

@@ -427,6 +427,84 @@ int32_t mh_eval_values_many(mh_ctx* ctx, const mh_tapeset* ts, const uint32_t* t
 /* Kernel launches mh_eval_values_many has made on this context (a test / latency counter).     */
 int32_t mh_ctx_eval_launches(const mh_ctx* ctx, uint64_t* launches);
 
+/* ---- repair of near-miss rows (no reference counterpart; DESIGN.md §6 "repair") ----------------
+ * A query's harvested sets override each other: a row satisfies one conjunct's inversion and
+ * breaks another's.  The repair step scores the rows a round left in the buffer by the conjuncts
+ * they fail, keeps the best, and regenerates only the columns of ONE failing conjunct per child
+ * row around them.  Opt-in (Sieve(repair_rounds=...)); nothing else in the library calls it.
+ *
+ * Conjunct plan (host only).  `nodes` is a root tape whose root is a Bool conjunction.  Its AND
+ * leaves are flattened left to right exactly as the guide harvest flattens them; the leaves that
+ * read at least one column of group_cols (n_group_cols == 0: at least one column at all) are kept,
+ * in that order, and each becomes a self-contained tape (its cone, nodes in ascending order,
+ * operands re-indexed; VAR imm0 / CONST imm0 unchanged, so the query's columns and constants
+ * apply).  More than max_conjuncts kept leaves, or fewer than 2: MH_E_UNSUPPORTED (the caller
+ * skips repair).  On MH_OK *info points into *out until mh_conjuncts_free(*out).                */
+typedef struct mh_conjuncts mh_conjuncts;
+typedef struct {
+    const mh_node* nodes;        /* the conjunct tapes back to back                              */
+    const uint64_t* tape_off;    /* [n_conjuncts + 1] (node indices, as mh_tapes_compile takes)  */
+    const uint32_t* leaf;        /* [n_conjuncts] the conjunct's node id in the root tape        */
+    const uint32_t* col_off;     /* [n_conjuncts + 1] ranges of `cols`                           */
+    const uint32_t* cols;        /* the columns each conjunct reads, ascending                   */
+    uint32_t n_conjuncts;
+    uint32_t pad;
+} mh_conjuncts_info;
+int32_t mh_conjuncts_build(const mh_node* nodes, uint32_t n_nodes, const uint32_t* group_cols,
+                           uint32_t n_group_cols, uint32_t max_conjuncts, mh_conjuncts** out,
+                           mh_conjuncts_info* info);
+int32_t mh_conjuncts_free(mh_conjuncts* c);
+/* Set provenance of a harvested guide: out[j] = the root-tape node id of the conjunct whose
+ * inversion, equality / constant pairs or copy alternatives made set j (mh_conjuncts_info.leaf
+ * holds the same ids), or 0xFFFFFFFF for the parent set, hint sets and the interval sets several
+ * conjuncts share.  n_sets must be the guide's.  The guide arrays are unaffected.                */
+#define MH_NO_CONJUNCT 0xFFFFFFFFu
+int32_t mh_harvest_set_conjuncts(const mh_harvest* h, uint32_t* out, uint32_t n_sets);
+
+/* Device side.  An mh_repair belongs to a ctx and owns the mask, score and elite buffers, sized
+ * at creation: max_conjuncts 1..4096, max_rows 1..65536, max_elites 1..256.  Every call is
+ * refused with MH_E_INVALID, before anything is launched, when an argument exceeds them.
+ *
+ * mh_repair_score: conjunct tapes [tape_first, tape_first + tape_count) of a compiled conjunct
+ * tape set over rows [row_first, row_first + row_count) of `as`, through the interpreter (one
+ * launch per kernel-variant bucket on the ctx stream, each wave writing its 64-row Bool mask per
+ * tape); then fail_count[r] = the conjuncts row row_first + r fails.  The masks stay resident for
+ * mh_repair_select.  fail_count_out ([row_count], may be NULL) receives the counts (blocks).
+ *
+ * mh_repair_select: the n = min(k, row_count) scored rows with the smallest (fail_count, row),
+ * ascending; ties go to the lower row.  For each, pick = the ordinal (tape - tape_first) of its
+ * (h mod fail_count)-th failing conjunct in ordinal order, h = mh_gen_limb(seed ^
+ * 0x3C6EF372FE94F82B, 0, row, 0), or MH_NO_CONJUNCT when it fails none.  `row` is the buffer row.
+ * The elites are copied to out[0..n) and kept on the device for mh_repair_mutate.  Blocks.
+ *
+ * mh_repair_mutate: for elite slot s < n and child c < per, row i = s * per + c of dst (!= src,
+ * the same column count) gets every column of src row elite[s].row; child 0 stays that copy, and
+ * so does every child of an elite whose pick is MH_NO_CONJUNCT.  Otherwise, with t = pick and
+ * draw index g = global_base + i: when flags has MH_MUTATE_REDRAW or no set j has set_conj[j] ==
+ * t, every column conj_cols[conj_col_off[t] .. conj_col_off[t + 1]) first gets
+ * mh_assign_generate_guided's base value for (seed, column, g) (small / uniform / pool, masked
+ * to the column width); then the sets with set_conj[j] == t are applied in set order by the
+ * generator's own rule (the draw against set_prob, value and MH_GUIDE_COPY entries).  set_conj is
+ * [guide->n_sets] conjunct ordinals (or MH_NO_CONJUNCT), n_conjuncts the plan's.  Blocks.        */
+typedef struct mh_repair mh_repair;
+typedef struct mh_elite {
+    uint32_t row;         /* buffer row                                                          */
+    uint32_t fail_count;
+    uint32_t pick;        /* conjunct ordinal to mutate, or MH_NO_CONJUNCT                       */
+} mh_elite;
+#define MH_MUTATE_REDRAW 1u
+int32_t mh_repair_create(mh_ctx* ctx, uint32_t max_conjuncts, uint32_t max_rows,
+                         uint32_t max_elites, mh_repair** out);
+int32_t mh_repair_destroy(mh_repair* r);
+int32_t mh_repair_score(mh_repair* r, const mh_tapeset* ts, uint32_t tape_first,
+                        uint32_t tape_count, const mh_assign* as, uint64_t row_first,
+                        uint64_t row_count, uint32_t* fail_count_out);
+int32_t mh_repair_select(mh_repair* r, uint32_t k, uint64_t seed, mh_elite* out, uint32_t* n_out);
+int32_t mh_repair_mutate(mh_repair* r, const mh_assign* src, mh_assign* dst, const mh_guide* guide,
+                         const uint32_t* set_conj, const uint32_t* conj_col_off,
+                         const uint32_t* conj_cols, uint32_t n_conjuncts, uint32_t per,
+                         uint32_t flags, uint64_t seed, uint64_t global_base);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* ---- native-code path (no reference counterpart: replaces the interpreter for throughput runs)
  * mh_tapes_jit compiles every tape of the set that the JIT covers to gfx950 machine code -- one

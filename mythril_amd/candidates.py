@@ -18,6 +18,10 @@ the query's own terms:
 The device generator (``mh_assign_generate_guided``, restated in oracle/guided_gen.py) draws
 each column from {small, uniform, pool} and then applies one alternative of each set with the
 set's probability, from a counter-based RNG, so any row range regenerates independently.
+
+The native harvest (csrc/harvest.cpp) also records which conjunct contributed each set
+(``mh_harvest_set_conjuncts``, for the repair step of sieve.py); this Python twin keeps no such
+tags: they do not change the guide's arrays, which is all the twin is compared on.
 """
 from __future__ import annotations
 

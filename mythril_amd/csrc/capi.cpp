@@ -1016,11 +1016,9 @@ int32_t mh_assign_generate(mh_assign* as, uint64_t seed, uint64_t global_base) {
     return MH_OK;
 }
 
-int32_t mh_assign_generate_guided(mh_assign* as, uint64_t seed, uint64_t global_base,
-                                  uint64_t first, uint64_t count, const mh_guide* g) {
-    if (!as || !g) return set_err(MH_E_INVALID, "null argument");
-    if (first > as->capacity || count > as->capacity - first)
-        return set_err(MH_E_INVALID, "row range out of bounds");
+// The guide checked, packed and queued for upload into `as`'s guide buffer (on the ctx stream):
+// *k = its device form.  Shared by the generator and the repair step's mutate (mh_repair_mutate).
+static int32_t stage_guide(mh_assign* as, const mh_guide* g, mh::KGuide* out) {
     if (g->n_cols > as->n_vars) return set_err(MH_E_INVALID, "guide has more columns than the buffer");
     if (g->n_cols && (!g->col_width || !g->pool_off))
         return set_err(MH_E_INVALID, "guide: null column arrays");
@@ -1131,6 +1129,17 @@ int32_t mh_assign_generate_guided(mh_assign* as, uint64_t seed, uint64_t global_
     k.entry_col = as->d_guide + o_ecol;
     k.entry_val = as->d_guide + o_eval;
     k.span_words = (uint32_t)(o_eval - o_prob);
+    *out = k;
+    return MH_OK;
+}
+
+int32_t mh_assign_generate_guided(mh_assign* as, uint64_t seed, uint64_t global_base,
+                                  uint64_t first, uint64_t count, const mh_guide* g) {
+    if (!as || !g) return set_err(MH_E_INVALID, "null argument");
+    if (first > as->capacity || count > as->capacity - first)
+        return set_err(MH_E_INVALID, "row range out of bounds");
+    mh::KGuide k;
+    if (int32_t r = stage_guide(as, g, &k)) return r;
     MH_HIP(mh::launch_generate_guided(as->d, as->stride, first, count, seed, global_base, k,
                                       as->ctx->stream));
     return MH_OK;
@@ -1774,6 +1783,220 @@ int32_t mh_ctx_kernel_time(mh_ctx* ctx, double* total_ms, uint64_t* launches) {
     *total_ms = sum;
     if (err != hipSuccess)
         return set_err(MH_E_DEVICE, std::string("kernel timing: ") + hipGetErrorString(err));
+    return MH_OK;
+}
+
+// ---- repair of near-miss rows (include/mythril_hip.h; kernels in repair.hip) -------------------
+struct mh_repair {
+    mh_ctx* ctx = nullptr;
+    uint32_t max_conj = 0, max_rows = 0, max_elites = 0;
+    unsigned long long* d_masks = nullptr;  // [conjunct][wave of the scored run]
+    size_t mask_words = 0;
+    uint32_t* d_fail = nullptr;             // [max_rows]
+    mh_elite* d_elites = nullptr;           // [max_elites]
+    uint32_t* d_plan = nullptr;             // mutate: set_conj | conj_col_off | conj_cols (grow-only)
+    size_t plan_words = 0;
+    std::vector<uint32_t> h_plan;
+    // the last score and select
+    bool scored = false, selected = false;
+    uint32_t n_conj = 0, row_first = 0, row_count = 0;
+    uint64_t stride = 0;
+    std::vector<mh_elite> elites;
+};
+
+static int32_t repair_span(mh_ctx* ctx, bool end) {  // mh_ctx_kernel_time counts repair launches too
+    if (!ctx->timing) return MH_OK;
+    if (!end) {
+        std::pair<hipEvent_t, hipEvent_t> sp{nullptr, nullptr};
+        MH_HIP(hipEventCreate(&sp.first));
+        MH_HIP(hipEventCreate(&sp.second));
+        ctx->spans.push_back(sp);
+        MH_HIP(hipEventRecord(sp.first, ctx->stream));
+    } else {
+        MH_HIP(hipEventRecord(ctx->spans.back().second, ctx->stream));
+    }
+    return MH_OK;
+}
+
+int32_t mh_repair_create(mh_ctx* ctx, uint32_t max_conjuncts, uint32_t max_rows,
+                         uint32_t max_elites, mh_repair** out) {
+    if (!ctx || !out) return set_err(MH_E_INVALID, "null argument");
+    *out = nullptr;
+    if (max_conjuncts < 1 || max_conjuncts > 4096 || max_rows < 1 || max_rows > 65536 ||
+        max_elites < 1 || max_elites > 256)
+        return set_err(MH_E_INVALID, "mh_repair_create: sizes outside 1..4096 conjuncts, "
+                                     "1..65536 rows, 1..256 elites");
+    if (int32_t r = use_device(ctx)) return r;
+    mh_repair* r = new (std::nothrow) mh_repair();
+    if (!r) return set_err(MH_E_NOMEM, "repair allocation");
+    r->ctx = ctx;
+    ++ctx->children;
+    r->max_conj = max_conjuncts;
+    r->max_rows = max_rows;
+    r->max_elites = max_elites;
+    // a run's mask stride is its waves, rounded up to whole workgroups (at most 16 waves each)
+    r->mask_words = (size_t)max_conjuncts * (max_rows / 64 + 16);
+    hipError_t e = hipMalloc(&r->d_masks, r->mask_words * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(&r->d_fail, (size_t)max_rows * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&r->d_elites, (size_t)max_elites * sizeof(mh_elite));
+    if (e != hipSuccess) {
+        mh_repair_destroy(r);
+        return set_err(MH_E_NOMEM, std::string("repair buffers: ") + hipGetErrorString(e));
+    }
+    *out = r;
+    return MH_OK;
+}
+
+int32_t mh_repair_destroy(mh_repair* r) {
+    if (!r) return MH_OK;
+    settle(r->ctx);
+    (void)hipSetDevice(r->ctx->device);
+    if (r->d_masks) (void)hipFree(r->d_masks);
+    if (r->d_fail) (void)hipFree(r->d_fail);
+    if (r->d_elites) (void)hipFree(r->d_elites);
+    if (r->d_plan) (void)hipFree(r->d_plan);
+    mh_ctx* ctx = r->ctx;
+    delete r;
+    ctx_unref(ctx);
+    return MH_OK;
+}
+
+int32_t mh_repair_score(mh_repair* r, const mh_tapeset* ts, uint32_t tape_first,
+                        uint32_t tape_count, const mh_assign* as, uint64_t row_first,
+                        uint64_t row_count, uint32_t* fail_count_out) {
+    if (!r) return set_err(MH_E_INVALID, "null handle");
+    mh_ctx* ctx = r->ctx;
+    if (int32_t rc = check_run_args(ctx, ts, tape_first, tape_count, as, row_first, row_count,
+                                    MH_MODE_COUNT_ALL))
+        return rc;
+    if (tape_count < 1 || tape_count > r->max_conj)
+        return set_err(MH_E_INVALID, "mh_repair_score: conjunct count outside 1..max_conjuncts");
+    if (row_count < 1 || row_count > r->max_rows || row_first + row_count > (1ull << 32))
+        return set_err(MH_E_INVALID, "mh_repair_score: row count outside 1..max_rows");
+    const uint64_t stride = mh::sieve_mask_stride(row_count);
+    if (stride * 64 < row_count || (uint64_t)tape_count * stride > r->mask_words)
+        return set_err(MH_E_INVALID, "mh_repair_score: the run's masks exceed the handle's buffer");
+    if (int32_t rc = use_device(ctx)) return rc;
+    mh::KParams p = make_params(ts, tape_first, as, row_first, row_count, 0, MH_MODE_COUNT_ALL);
+    p.masks = r->d_masks;
+    p.mask_base = tape_first;
+    p.mask_stride = stride;
+    // the conjunct tapes of each kernel-variant bucket inside the range, refused before a launch
+    const uint32_t *lo[mh::kNumVariants], *hi[mh::kNumVariants];
+    for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
+        const uint32_t* b = ts->ids.data() + ts->bucket_off[v];
+        const uint32_t* e = ts->ids.data() + ts->bucket_off[v + 1];
+        lo[v] = std::lower_bound(b, e, tape_first);
+        hi[v] = std::lower_bound(lo[v], e, tape_first + tape_count);
+        if (hi[v] != lo[v] && !mh::variant_fits(v, p.capacity)) return refuse_capacity(p.capacity);
+    }
+    r->scored = r->selected = false;
+    if (int32_t rc = repair_span(ctx, false)) return rc;
+    for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
+        if (hi[v] == lo[v]) continue;
+        mh::KParams q = p;
+        q.tape_ids = ts->d_ids + (lo[v] - ts->ids.data());
+        q.n_ids = (uint32_t)(hi[v] - lo[v]);
+        MH_HIP(mh::launch_sieve(q, v, ctx->stream));
+    }
+    MH_HIP(mh::launch_fail_count(r->d_masks, stride, tape_count, (uint32_t)row_count, r->d_fail,
+                                 ctx->stream));
+    if (int32_t rc = repair_span(ctx, true)) return rc;
+    r->n_conj = tape_count;
+    r->row_first = (uint32_t)row_first;
+    r->row_count = (uint32_t)row_count;
+    r->stride = stride;
+    r->scored = true;
+    if (fail_count_out) {
+        MH_HIP(hipMemcpyAsync(fail_count_out, r->d_fail, row_count * sizeof(uint32_t),
+                              hipMemcpyDeviceToHost, ctx->stream));
+        MH_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return MH_OK;
+}
+
+int32_t mh_repair_select(mh_repair* r, uint32_t k, uint64_t seed, mh_elite* out, uint32_t* n_out) {
+    if (!r || !out || !n_out) return set_err(MH_E_INVALID, "null argument");
+    *n_out = 0;
+    if (!r->scored) return set_err(MH_E_INVALID, "mh_repair_select: nothing scored");
+    if (k < 1 || k > r->max_elites)
+        return set_err(MH_E_INVALID, "mh_repair_select: k outside 1..max_elites");
+    mh_ctx* ctx = r->ctx;
+    if (int32_t rc = use_device(ctx)) return rc;
+    const uint32_t n = std::min(k, r->row_count);
+    r->selected = false;
+    if (int32_t rc = repair_span(ctx, false)) return rc;
+    MH_HIP(mh::launch_select(r->d_masks, r->stride, r->n_conj, r->d_fail, r->row_first,
+                             r->row_count, n, seed, r->d_elites, ctx->stream));
+    if (int32_t rc = repair_span(ctx, true)) return rc;
+    r->elites.assign(n, mh_elite{});
+    MH_HIP(hipMemcpyAsync(r->elites.data(), r->d_elites, n * sizeof(mh_elite),
+                          hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(hipStreamSynchronize(ctx->stream));
+    std::copy(r->elites.begin(), r->elites.end(), out);
+    *n_out = n;
+    r->selected = true;
+    return MH_OK;
+}
+
+int32_t mh_repair_mutate(mh_repair* r, const mh_assign* src, mh_assign* dst, const mh_guide* guide,
+                         const uint32_t* set_conj, const uint32_t* conj_col_off,
+                         const uint32_t* conj_cols, uint32_t n_conjuncts, uint32_t per,
+                         uint32_t flags, uint64_t seed, uint64_t global_base) {
+    if (!r || !src || !dst || !guide || !conj_col_off || (guide->n_sets && !set_conj))
+        return set_err(MH_E_INVALID, "null argument");
+    mh_ctx* ctx = r->ctx;
+    if (src->ctx != ctx || dst->ctx != ctx) return set_err(MH_E_INVALID, "handles of another ctx");
+    if (dst == src) return set_err(MH_E_INVALID, "mh_repair_mutate: dst is src");
+    if (!r->selected) return set_err(MH_E_INVALID, "mh_repair_mutate: no elites selected");
+    if (src->n_vars != dst->n_vars)
+        return set_err(MH_E_INVALID, "mh_repair_mutate: buffers of different column counts");
+    if (flags & ~MH_MUTATE_REDRAW) return set_err(MH_E_INVALID, "mh_repair_mutate: bad flags");
+    const uint32_t n_el = (uint32_t)r->elites.size();
+    if (per < 1 || (uint64_t)n_el * per > dst->capacity || (uint64_t)n_el * per > (1ull << 31))
+        return set_err(MH_E_INVALID, "mh_repair_mutate: children exceed dst's capacity");
+    if (n_conjuncts < 1 || n_conjuncts > r->max_conj)
+        return set_err(MH_E_INVALID, "mh_repair_mutate: conjunct count outside 1..max_conjuncts");
+    // every index the kernel follows is checked here: it trusts them
+    for (const mh_elite& e : r->elites)
+        if (e.row >= src->capacity || (e.pick != MH_NO_CONJUNCT && e.pick >= n_conjuncts))
+            return set_err(MH_E_INVALID, "mh_repair_mutate: the elites are not of this src / plan");
+    if (conj_col_off[0] != 0) return set_err(MH_E_INVALID, "mh_repair_mutate: conj_col_off[0] != 0");
+    for (uint32_t t = 0; t < n_conjuncts; ++t)
+        if (conj_col_off[t + 1] < conj_col_off[t])
+            return set_err(MH_E_INVALID, "mh_repair_mutate: conj_col_off not monotone");
+    const uint32_t n_cc = conj_col_off[n_conjuncts];
+    if (n_cc && !conj_cols) return set_err(MH_E_INVALID, "mh_repair_mutate: null conj_cols");
+    for (uint32_t q = 0; q < n_cc; ++q)
+        if (conj_cols[q] >= guide->n_cols)
+            return set_err(MH_E_INVALID, "mh_repair_mutate: conjunct column outside the guide");
+    for (uint32_t j = 0; j < guide->n_sets; ++j)
+        if (set_conj[j] != MH_NO_CONJUNCT && set_conj[j] >= n_conjuncts)
+            return set_err(MH_E_INVALID, "mh_repair_mutate: set tag outside the plan");
+    mh::KGuide k;
+    if (int32_t rc = stage_guide(dst, guide, &k)) return rc;  // checks the guide; uses the device
+    const size_t o_tag = 0, o_off = o_tag + guide->n_sets, o_cols = o_off + n_conjuncts + 1,
+                 words = o_cols + n_cc;
+    r->h_plan.assign(words, 0);
+    if (guide->n_sets) std::copy(set_conj, set_conj + guide->n_sets, r->h_plan.begin() + o_tag);
+    std::copy(conj_col_off, conj_col_off + n_conjuncts + 1, r->h_plan.begin() + o_off);
+    if (n_cc) std::copy(conj_cols, conj_cols + n_cc, r->h_plan.begin() + o_cols);
+    if (words > r->plan_words) {
+        if (r->d_plan) MH_HIP(hipFree(r->d_plan));
+        r->d_plan = nullptr;
+        r->plan_words = 0;
+        const size_t grow = std::max<size_t>({words, 2 * r->plan_words, (size_t)1 << 12});
+        MH_HIP(hipMalloc(&r->d_plan, grow * sizeof(uint32_t)));
+        r->plan_words = grow;
+    }
+    MH_HIP(hipMemcpyAsync(r->d_plan, r->h_plan.data(), words * sizeof(uint32_t),
+                          hipMemcpyHostToDevice, ctx->stream));
+    if (int32_t rc = repair_span(ctx, false)) return rc;
+    MH_HIP(mh::launch_mutate(src->d, src->stride, dst->d, dst->stride, dst->n_vars, r->d_elites,
+                             n_el, per, flags, seed, global_base, k, r->d_plan + o_tag,
+                             r->d_plan + o_off, r->d_plan + o_cols, ctx->stream));
+    if (int32_t rc = repair_span(ctx, true)) return rc;
+    MH_HIP(hipStreamSynchronize(ctx->stream));  // h_plan is pageable: done with it on return
     return MH_OK;
 }
 

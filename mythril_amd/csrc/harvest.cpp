@@ -330,6 +330,11 @@ struct Harvester {
     AVec<std::shared_ptr<const Alts>> hint_results;
     int n_hints = 0;
     std::vector<std::vector<std::vector<Copy>>> copy_sets;
+    // provenance (mh_harvest_set_conjuncts): per entry of `sets` / `copy_sets`, the root-tape
+    // node of the conjunct that contributed it, kNoConjunct for the parent and interval sets;
+    // out_tags: per emitted set, in the guide's set order (hint sets: kNoConjunct)
+    static constexpr uint32_t kNoConjunct = 0xFFFFFFFFu;
+    std::vector<uint32_t> set_tags, copy_tags, out_tags;
     std::vector<U> query_consts;
     // the last query's conjuncts and constants (sorted, unique), kept across a session's queries
     std::vector<uint32_t> last_conj;
@@ -387,6 +392,8 @@ struct Harvester {
         std::fill(hint_done.begin(), hint_done.end(), 0);
         n_hints = 0;
         copy_sets.clear();
+        set_tags.clear();
+        copy_tags.clear();
         query_consts.clear();
         consts_by_width.clear();
         const_ids_by_width.clear();
@@ -988,14 +995,20 @@ struct Harvester {
         }
         if (parent && !parent->empty())
             sets.push_back({kProbParent, std::make_shared<const Alts>(Alts{*parent})});
+        set_tags.assign(sets.size(), kNoConjunct);
         std::vector<char> seen_eq(nd.size(), 0);
         std::unordered_map<uint32_t, std::tuple<bool, uint32_t, uint32_t,
                                                 std::vector<std::vector<Copy>>>> eq_pairs;
+        uint32_t tag = kNoConjunct;  // the conjunct whose sets are being pushed
         auto replay = [&](const Contribution& c, int prob) {
             for (uint32_t id : c.hints) emit_hint(id);
-            if (c.set) sets.push_back({prob, c.set});
+            if (c.set) {
+                sets.push_back({prob, c.set});
+                set_tags.push_back(tag);
+            }
         };
         for (uint32_t cj : conj) {
+            tag = cj;
             auto cd = conj_done.find(nk(cj));
             if (cd != conj_done.end()) {
                 replay(cd->second, kProbDefault);
@@ -1008,6 +1021,7 @@ struct Harvester {
                     for (const Alt& a : alts.alts()) if (!a.empty()) kept.push_back(a);
                     c.set = std::make_shared<const Alts>(head(kept, kMaxAlts));
                     sets.push_back({kProbDefault, c.set});
+                    set_tags.push_back(tag);
                 }
                 conj_done.emplace(nk(cj), std::move(c));
             }
@@ -1034,7 +1048,10 @@ struct Harvester {
                 EqPlan& pl = pit->second;
                 if (pl.skip) continue;
                 if (!pl.copies.empty()) {
-                    if ((int)copy_sets.size() < kMaxSets / 4) copy_sets.push_back(pl.copies);
+                    if ((int)copy_sets.size() < kMaxSets / 4) {
+                        copy_sets.push_back(pl.copies);
+                        copy_tags.push_back(tag);
+                    }
                     continue;
                 }
                 const uint32_t x = pl.x, y = pl.y;
@@ -1061,6 +1078,7 @@ struct Harvester {
                         if (!both.empty() && !is_only_empty(both)) {
                             c.set = std::make_shared<const Alts>(head(both, kMaxAlts));
                             sets.push_back({kProbDefault / 2, c.set});
+                            set_tags.push_back(tag);
                         }
                     }
                     pl.by_const.emplace(kids[ki], std::move(c));
@@ -1081,15 +1099,26 @@ struct Harvester {
                 if (!r.none && !r.alts().empty())
                     for (const Alt& a : r.alts()) if (!a.empty()) out.push_back(a);
             }
-            if (!out.empty())
+            if (!out.empty()) {
                 sets.push_back({kProbDefault, std::make_shared<const Alts>(head(out, kMaxAlts))});
+                set_tags.push_back(kNoConjunct);
+            }
         }
         out_sets.clear();
+        out_tags.clear();
         const bool first_parent = parent && !parent->empty() && !sets.empty();
-        if (first_parent) out_sets.push_back({sets[0].first, sets[0].second.get()});
-        for (uint32_t id : prune_hints()) out_sets.push_back({kProbHint, &hint_alts[id]});
-        for (size_t i = first_parent ? 1 : 0; i < sets.size(); ++i)
+        if (first_parent) {
+            out_sets.push_back({sets[0].first, sets[0].second.get()});
+            out_tags.push_back(kNoConjunct);
+        }
+        for (uint32_t id : prune_hints()) {
+            out_sets.push_back({kProbHint, &hint_alts[id]});
+            out_tags.push_back(kNoConjunct);
+        }
+        for (size_t i = first_parent ? 1 : 0; i < sets.size(); ++i) {
             out_sets.push_back({sets[i].first, sets[i].second.get()});
+            out_tags.push_back(set_tags[i]);
+        }
         pools.assign(n_cols, {});
         // first occurrences in order, at most kMaxPool per column; the duplicate test compares
         // a 64-bit digest of each value before the value itself (a long path's sets repeat values)
@@ -1114,8 +1143,11 @@ struct Harvester {
             for (const U& v : {U::of(0), U::of(1), mask(w), shl(U::of(1), w - 1)}) add_pool(c, lo256(v));
         }
         if ((int)out_sets.size() > kMaxSets) out_sets.resize(kMaxSets);
+        out_tags.resize(out_sets.size());
         out_copies = copy_sets;
         if ((int)out_copies.size() > kMaxSets / 4) out_copies.resize(kMaxSets / 4);
+        out_tags.insert(out_tags.end(), copy_tags.begin(),
+                        copy_tags.begin() + (long)out_copies.size());
     }
 
     // candidates.py _bound_of: conjunct n bounds a symbolic term to [lo, hi] (unsigned,
@@ -1235,6 +1267,7 @@ struct mh_harvest {  // owns the arrays an mh_guide from mh_guide_harvest points
     std::vector<uint32_t> pool_off, pool, set_off, alt_off, entry_col, entry_val;
     std::vector<uint8_t> set_prob;
     std::vector<uint16_t> width16;
+    std::vector<uint32_t> set_conj;  // mh_harvest_set_conjuncts
 };
 
 int32_t mh_detail_set_err(int32_t code, const char* msg);  // capi.cpp
@@ -1295,6 +1328,7 @@ int32_t harvest_into(Harvester& h, const mh_node* nodes, uint32_t n_nodes, const
     h.harvest(n_nodes - 1, n_parent ? &parent : nullptr, pools, sets, copies);
     auto r = std::make_unique<mh_harvest>();
     r->width16.assign(h.widths.begin(), h.widths.end());
+    r->set_conj = h.out_tags;
     // sized exactly first (a long path's guide holds thousands of entries), then written in place
     size_t n_pool = 0, n_alt = 0, n_ent = 0;
     for (const auto& p : pools) n_pool += p.size();
@@ -1546,6 +1580,14 @@ extern "C" int32_t mh_guide_harvest_with(mh_harvester* s, const mh_node* nodes, 
         s->nodes.clear();
         return mh_detail_set_err(MH_E_NOMEM, "host allocation failed");
     }
+}
+
+extern "C" int32_t mh_harvest_set_conjuncts(const mh_harvest* h, uint32_t* out, uint32_t n_sets) {
+    if (!h || (!out && n_sets)) return mh_detail_set_err(MH_E_INVALID, "null argument");
+    if (n_sets != h->set_conj.size())
+        return mh_detail_set_err(MH_E_INVALID, "n_sets is not the guide's");
+    std::copy(h->set_conj.begin(), h->set_conj.end(), out);
+    return MH_OK;
 }
 
 extern "C" int32_t mh_harvest_free(mh_harvest* h) {

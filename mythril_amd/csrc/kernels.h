@@ -93,6 +93,25 @@ hipError_t launch_combine(const unsigned long long* masks, uint64_t stride, cons
                           uint32_t n_split, uint32_t mask_base, uint32_t result_base,
                           uint64_t index0, unsigned long long* first_hit,
                           unsigned long long* hit_count, hipStream_t stream);
+// the repair step (repair.hip; include/mythril_hip.h mh_repair_*).  masks[conjunct][wave] are a
+// masks-mode run's (mask_base = the first conjunct tape), `stride` its sieve_mask_stride.
+// fail[r] = the conjuncts row r of the run fails
+hipError_t launch_fail_count(const unsigned long long* masks, uint64_t stride, uint32_t n_conj,
+                             uint32_t row_count, uint32_t* fail, hipStream_t stream);
+// elites[0..n_sel): the rows with the smallest (fail, row), row = row_first + r, and their picks;
+// n_sel <= min(row_count, 256); one workgroup, (n_conj + 1) words of dynamic LDS
+hipError_t launch_select(const unsigned long long* masks, uint64_t stride, uint32_t n_conj,
+                         const uint32_t* fail, uint32_t row_first, uint32_t row_count,
+                         uint32_t n_sel, uint64_t seed, mh_elite* elites, hipStream_t stream);
+// rows [0, n_elites * per) of dst: the elites' src rows, children 1.. with their pick's columns
+// regenerated (set_conj [g.n_sets], conj_col_off / conj_cols on the device; the caller has
+// checked every index: the kernel trusts them)
+hipError_t launch_mutate(const uint32_t* src, uint64_t src_stride, uint32_t* dst,
+                         uint64_t dst_stride, uint32_t n_vars, const mh_elite* elites,
+                         uint32_t n_elites, uint32_t per, uint32_t flags, uint64_t seed,
+                         uint64_t base, const KGuide& g, const uint32_t* set_conj,
+                         const uint32_t* conj_col_off, const uint32_t* conj_cols,
+                         hipStream_t stream);
 hipError_t launch_microbench(uint32_t kind, uint32_t iters, uint32_t blocks, uint32_t* sink,
                              hipStream_t stream);
 

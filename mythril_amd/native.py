@@ -122,6 +122,17 @@ SIGNATURES = {
     "mh_terms_sizes": (C.c_int32, [_vp, _u64p]),
     "mh_query_build": (C.c_int32, [_vp, _u32p, C.c_uint32, C.POINTER(_vp), _vp]),
     "mh_query_free": (C.c_int32, [_vp]),
+    "mh_conjuncts_build": (C.c_int32, [_vp, C.c_uint32, _u32p, C.c_uint32, C.c_uint32,
+                                       C.POINTER(_vp), _vp]),
+    "mh_conjuncts_free": (C.c_int32, [_vp]),
+    "mh_harvest_set_conjuncts": (C.c_int32, [_vp, _u32p, C.c_uint32]),
+    "mh_repair_create": (C.c_int32, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    "mh_repair_destroy": (C.c_int32, [_vp]),
+    "mh_repair_score": (C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
+                                    C.c_uint64, _u32p]),
+    "mh_repair_select": (C.c_int32, [_vp, C.c_uint32, C.c_uint64, _vp, _u32p]),
+    "mh_repair_mutate": (C.c_int32, [_vp, _vp, _vp, _vp, _u32p, _u32p, _u32p, C.c_uint32,
+                                     C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
 }
 
 # mh_smt_record / mh_smt_result (include/mythril_hip.h)
@@ -220,6 +231,20 @@ def _limb_rows(vals) -> np.ndarray:
     return np.frombuffer(buf, dtype="<u4").reshape(-1, 8).copy()
 
 
+def _guide_struct(arrays: dict):
+    """An mh_guide over guide arrays (candidates.Guide.arrays()), and the arrays it points into
+    (the caller keeps them alive for the call)."""
+    dts = dict(width=np.uint16, set_prob=np.uint8)
+    a = {k: np.ascontiguousarray(v, dtype=dts.get(k, np.uint32)) for k, v in arrays.items()}
+    n_cols = len(a["width"])
+    n_sets = len(a["set_off"]) - 1
+    g = Guide(n_cols, a["width"].ctypes.data_as(C.POINTER(C.c_uint16)), _ptr(a["pool_off"]),
+              _ptr(a["pool"]), n_sets, a["set_prob"].ctypes.data_as(C.POINTER(C.c_uint8)),
+              _ptr(a["set_off"]), _ptr(a["alt_off"]), _ptr(a["entry_col"]),
+              _ptr(a["entry_val"]))
+    return g, a
+
+
 def _guide_arrays(g: "Guide") -> dict:
     """The arrays of an mh_guide the library owns, copied (one memcpy each)."""
     def arr(p, n, dt=np.uint32):
@@ -247,6 +272,14 @@ class GuideHandle:
 
     def arrays(self) -> dict:
         return _guide_arrays(self.guide)
+
+    def set_conjuncts(self) -> np.ndarray:
+        """Per set of the guide: the root-tape node id of the conjunct that contributed it, or
+        NO_CONJUNCT for the parent, hint and shared interval sets (mh_harvest_set_conjuncts)."""
+        n = int(self.guide.n_sets)
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        _check(self.lib.mh_harvest_set_conjuncts(self.h, _ptr(out), n))
+        return out[:n]
 
     def close(self) -> None:
         if self.h:
@@ -999,13 +1032,7 @@ class Assignments:
                         count: Optional[int] = None) -> None:
         """Rows [first, first+count) from a guide (mythril_amd.candidates.Guide.arrays())."""
         count = self.capacity - first if count is None else count
-        a = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
-        n_cols = len(a["width"])
-        n_sets = len(a["set_off"]) - 1
-        g = Guide(n_cols, a["width"].ctypes.data_as(C.POINTER(C.c_uint16)), _ptr(a["pool_off"]),
-                  _ptr(a["pool"]), n_sets, a["set_prob"].ctypes.data_as(C.POINTER(C.c_uint8)),
-                  _ptr(a["set_off"]), _ptr(a["alt_off"]), _ptr(a["entry_col"]),
-                  _ptr(a["entry_val"]))
+        g, _keep = _guide_struct(arrays)
         _check(self.ctx.lib.mh_assign_generate_guided(self.h, seed, global_base, first, count,
                                                       C.byref(g)))
 
@@ -1098,6 +1125,126 @@ def eval_values_many(ctx: Context, tapes: CompiledTapes, ids: Sequence[int], ass
     _check(ctx.lib.mh_eval_values_many(ctx.h, tapes.h, _ptr(ids_a), len(ids_a), assign.h, row,
                                        _ptr(out)))
     return out[:len(ids_a)]
+
+
+# ---- repair of near-miss rows (include/mythril_hip.h mh_conjuncts_* / mh_repair_*) -------------
+NO_CONJUNCT = 0xFFFFFFFF
+MUTATE_REDRAW = 1
+ELITE_DTYPE = np.dtype([("row", "<u4"), ("fail_count", "<u4"), ("pick", "<u4")])  # mh_elite
+
+
+class ConjunctsInfo(C.Structure):
+    """mh_conjuncts_info (include/mythril_hip.h)."""
+
+    _fields_ = [("nodes", _vp), ("tape_off", _u64p), ("leaf", _u32p), ("col_off", _u32p),
+                ("cols", _u32p), ("n_conjuncts", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class ConjunctPlan:
+    """mh_conjuncts_build's result, copied out: one tape per kept AND leaf of a root tape
+    (``tapes``), each leaf's node id in the root tape (``leaf``) and the columns it reads
+    (``cols`` ascending per conjunct; ``col_off`` / ``cols_flat`` as the library lays them out)."""
+
+    def __init__(self, nodes: np.ndarray, group_cols: Sequence[int] = (),
+                 max_conjuncts: int = 4096):
+        lib = load()
+        nodes = np.ascontiguousarray(nodes, dtype=NODE_DTYPE)
+        gc = np.ascontiguousarray(list(group_cols), dtype=np.uint32)
+        h, info = C.c_void_p(), ConjunctsInfo()
+        _check(lib.mh_conjuncts_build(nodes.ctypes.data, len(nodes), _ptr(gc), len(gc),
+                                      max_conjuncts, C.byref(h), C.byref(info)))
+        try:
+            n = int(info.n_conjuncts)
+            off = np.ctypeslib.as_array(info.tape_off, shape=(n + 1,)).copy()
+            flat = np.frombuffer(C.string_at(info.nodes, int(off[-1]) * NODE_DTYPE.itemsize),
+                                 dtype=NODE_DTYPE).copy()
+            self.n = n
+            self.tape_off = off
+            self.nodes = flat
+            self.tapes = [flat[int(off[i]):int(off[i + 1])] for i in range(n)]
+            self.leaf = np.ctypeslib.as_array(info.leaf, shape=(n,)).copy()
+            self.col_off = np.ctypeslib.as_array(info.col_off, shape=(n + 1,)).copy()
+            nc = int(self.col_off[-1])
+            self.cols_flat = np.ctypeslib.as_array(info.cols, shape=(max(nc, 1),)).copy()[:nc]
+            self.cols = [self.cols_flat[int(self.col_off[i]):int(self.col_off[i + 1])].tolist()
+                         for i in range(n)]
+        finally:
+            lib.mh_conjuncts_free(h)
+
+    def set_ordinals(self, set_conj: np.ndarray) -> np.ndarray:
+        """A guide's set tags (GuideHandle.set_conjuncts: root-tape leaf ids) as ordinals of
+        this plan; NO_CONJUNCT for untagged sets and for leaves the plan did not keep."""
+        first = {}
+        for i, leaf in enumerate(self.leaf.tolist()):
+            first.setdefault(leaf, i)
+        return np.array([first.get(int(t), NO_CONJUNCT) for t in set_conj], dtype=np.uint32)
+
+
+class Repair:
+    """mh_repair: the mask, score and elite buffers of the repair step, bound to a Context."""
+
+    def __init__(self, ctx: Context, max_conjuncts: int, max_rows: int, max_elites: int):
+        self.ctx = ctx
+        self.max_conjuncts, self.max_rows, self.max_elites = max_conjuncts, max_rows, max_elites
+        h = C.c_void_p()
+        _check(ctx.lib.mh_repair_create(ctx.h, max_conjuncts, max_rows, max_elites, C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            self.ctx.lib.mh_repair_destroy(self.h)
+            self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def repair_open(ctx: Context, max_conjuncts: int, max_rows: int, max_elites: int) -> Repair:
+    return Repair(ctx, max_conjuncts, max_rows, max_elites)
+
+
+def repair_score(rep: Repair, tapes: CompiledTapes, assign: Assignments, *, tape_first: int = 0,
+                 tape_count: Optional[int] = None, row_first: int = 0,
+                 row_count: Optional[int] = None, counts: bool = False) -> Optional[np.ndarray]:
+    """mh_repair_score: the conjunct tapes over the rows; with counts=True the per-row
+    fail_count (u32 [row_count]) is copied out."""
+    tc = tapes.n_tapes - tape_first if tape_count is None else tape_count
+    rc = assign.capacity - row_first if row_count is None else row_count
+    out = np.zeros(max(rc, 1), dtype=np.uint32) if counts else None
+    _check(rep.ctx.lib.mh_repair_score(rep.h, tapes.h, tape_first, tc, assign.h, row_first, rc,
+                                       _ptr(out) if counts else None))
+    return out[:rc] if counts else None
+
+
+def repair_select(rep: Repair, k: int, seed: int) -> np.ndarray:
+    """mh_repair_select: the best min(k, rows) rows as an ELITE_DTYPE array."""
+    out = np.zeros(max(k, 1), dtype=ELITE_DTYPE)
+    n = C.c_uint32()
+    _check(rep.ctx.lib.mh_repair_select(rep.h, k, seed, out.ctypes.data_as(C.c_void_p),
+                                        C.byref(n)))
+    return out[:n.value]
+
+
+def repair_mutate(rep: Repair, src: Assignments, dst: Assignments, guide, set_conj, col_off,
+                  cols, per: int, *, flags: int = 0, seed: int = 0, global_base: int = 0) -> None:
+    """mh_repair_mutate: rows [0, elites * per) of dst from the selected elites' rows of src.
+    `guide`: a GuideHandle or guide arrays; set_conj: conjunct ordinal per set of the guide
+    (ConjunctPlan.set_ordinals); col_off / cols: ConjunctPlan.col_off / cols_flat."""
+    if isinstance(guide, GuideHandle):
+        g, keep = guide.guide, None
+    else:
+        g, keep = _guide_struct(guide)
+    sc = np.ascontiguousarray(set_conj, dtype=np.uint32)
+    co = np.ascontiguousarray(col_off, dtype=np.uint32)
+    cc = np.ascontiguousarray(cols, dtype=np.uint32)
+    if len(sc) != int(g.n_sets):
+        raise ValueError("set_conj has %d entries for a guide of %d sets" % (len(sc), g.n_sets))
+    _check(rep.ctx.lib.mh_repair_mutate(rep.h, src.h, dst.h, C.byref(g), _ptr(sc), _ptr(co),
+                                        _ptr(cc), len(co) - 1, per, flags, seed, global_base))
+    del keep
 
 
 def eval_launches(ctx: Context) -> int:

@@ -44,6 +44,7 @@ class Witness:
     values: Dict[str, int]             # column name -> value
     index: int = 0                     # global candidate index that satisfied the query
     rounds: int = 0
+    repaired: bool = False             # a group's row came from the repair step (Sieve._repair)
 
 
 @dataclass
@@ -421,7 +422,8 @@ class Sieve:
     def __init__(self, device: int = 0, rows: int = 1 << 16, max_rounds: int = 2,
                  seed: int = 0x5EED5EED, budget_s: float = 0.25, first_rows: Optional[int] = None,
                  native_query: bool = True, second_round: Optional[str] = None,
-                 keccak_second_chance: Optional[bool] = None):
+                 keccak_second_chance: Optional[bool] = None, repair_rounds: int = 0,
+                 repair_elites: Optional[int] = None, repair_children: Optional[int] = None):
         self.ctx = native.Context(device)
         # host stages by the native query compiler (csrc/query.cpp); False: the Python stages
         # (lower.py, buckets, local_tapeset) it is checked against (tests/test_query_native.py)
@@ -492,8 +494,40 @@ class Sieve:
         # this one harvests the guide: the harvest is host-only, both only read the query's
         # tapes, and the round needs both (SIEVE_OVERLAP=0: one after the other)
         self.overlap = os.environ.get("SIEVE_OVERLAP", "1") != "0"
+        # repair of near-miss rows (Sieve._repair): iterations per unsolved group after
+        # an attempt's ordinary rounds; 0 (the default) runs none of it.  SIEVE_REPAIR overrides.
+        self.repair_rounds = int(os.environ.get("SIEVE_REPAIR", repair_rounds))
+        # K elites x `per` children each: 64 x 64 = 4096 rows, the short-run launch shape (64
+        # waves, one per SIMD of 64 CUs, as first_rows above)
+        self.repair_elites = min(256, max(1, int(
+            os.environ.get("SIEVE_REPAIR_ELITES", 64) if repair_elites is None else repair_elites)))
+        self.repair_children = max(1, int(
+            os.environ.get("SIEVE_REPAIR_CHILDREN", 64) if repair_children is None
+            else repair_children))
+        # a group stops when its best fail_count has not decreased for this many iterations, and
+        # is not started when the best row of the first score fails more conjuncts than max_fail.
+        # Tuned on the planted random family (20 paths x 16): an iteration costs tens
+        # of microseconds of device time, so far rows are worth starting from (max_fail 4 -> 16:
+        # recall 0.811 -> 0.840) and the stall rule is what ends a hopeless group (3 -> 2: the
+        # same recall, 0.3 ms off the miss p50; 1 loses 4 points)
+        self.repair_stall = int(os.environ.get("SIEVE_REPAIR_STALL", "2"))
+        self.repair_max_fail = int(os.environ.get("SIEVE_REPAIR_MAX_FAIL", "16"))
+        self.repair_max_conjuncts = int(os.environ.get("SIEVE_REPAIR_MAX_CONJUNCTS", "512"))
+        # of the rows the last round left in the buffer, the first this many are scored: 4096
+        # (the short-run launch shape) found better elites than all 16384 / 65536 -- the later
+        # rows' best are no nearer, and K is fixed -- 0.840 -> 0.862 on the same workload
+        self.repair_score_rows = min(1 << 16, max(1, int(
+            os.environ.get("SIEVE_REPAIR_SCORE_ROWS", "4096"))))
+        self.repairer = None                                  # native.Repair, made on first use
+        self.assign2: Optional[native.Assignments] = None     # the children's buffer
 
     def close(self) -> None:
+        if self.repairer is not None:
+            self.repairer.close()
+            self.repairer = None
+        if self.assign2 is not None:
+            self.assign2.close()
+            self.assign2 = None
         if self.assign is not None:
             self.assign.close()
             self.assign = None
@@ -940,6 +974,7 @@ class Sieve:
             values: Dict[str, int] = {}
             solved = [False] * len(group_cols)
             first_index = None
+            last_n = 0
             offset = (1 << 23) if keccak_reads else 0
             # the incremental round: the parent's witness under the newest root's conjuncts'
             # sets only (the parent's conjuncts hold there already), instead of the 2^16-row
@@ -985,6 +1020,7 @@ class Sieve:
                 self.last_rounds["rounds"] = rnd + 1
                 base = (self.stats.queries << 24) + offset
                 offset += n
+                last_n = n
                 tb = time.perf_counter()
                 # a later round runs only the tapes from the first to the last unsolved group
                 g0 = solved.index(False)
@@ -1023,6 +1059,24 @@ class Sieve:
                     return Witness(schema, values, first_index, rnd + 1), schema, False
                 if time.perf_counter() - t0 > budget:
                     break
+            if (self.repair_rounds > 0 and last_n and not all(solved)
+                    and time.perf_counter() - t0 <= budget):
+                base = (self.stats.queries << 24) + offset
+                hit = self._repair(root_nodes, ts, ct, guide, assign, last_n, columns, group_cols,
+                                   solved, values, base, budget, t0)
+                if hit is not None:
+                    first_index = hit if first_index is None else min(first_index, hit)
+                if all(solved):
+                    for c in columns:
+                        values.setdefault(c, 0)
+                    if defs:
+                        td = time.perf_counter()
+                        got = self.eval_definitions(b, defs, columns, values)
+                        for (c, _), v in zip(defs, got):
+                            values[c] = v
+                        st.add("definitions", time.perf_counter() - td)
+                    return (Witness(schema, values, first_index, self.last_rounds["rounds"],
+                                    repaired=True), schema, False)
             kec = any(not solved[g] and _reads_keccak(ts.tapes[g].nodes)
                       for g in range(len(solved)))
             return None, schema, kec
@@ -1032,6 +1086,120 @@ class Sieve:
             if inc_guide is not None:
                 inc_guide.close()
             self.stats.device_s += time.perf_counter() - t1
+
+    def _repair(self, root_nodes, ts, ct, guide, assign, n_rows, columns, group_cols, solved,
+                values, base, budget, t0):
+        """The repair step, after an attempt's ordinary rounds left groups unsolved:
+        per unsolved group, the rows the last round left in `assign` are scored by the group's
+        conjuncts they fail (mh_repair_score over the conjunct plan's tapes), the best K kept
+        (mh_repair_select) and `per` children made of each with ONE failing conjunct's columns
+        regenerated from that conjunct's own sets (mh_repair_mutate); the group's tape decides
+        over the children as in an ordinary round, and the children are scored for the next
+        iteration.  Fills `values` / `solved` for the groups it answers; returns the smallest
+        hit index or None."""
+        st = self.stats
+        ex = st.extra
+        K, per = self.repair_elites, self.repair_children
+        n_rows = min(n_rows, self.repair_score_rows)
+        lr = self.last_rounds
+        lr["repair"] = 0
+        first_hit = None
+        set_leaf = None
+        for g in range(len(solved)):
+            if solved[g] or not group_cols[g]:  # (a ground group has no column to repair)
+                continue
+            if time.perf_counter() - t0 > budget:
+                break
+            tr = time.perf_counter()
+            try:
+                plan = native.ConjunctPlan(root_nodes, group_cols[g] if len(group_cols) > 1 else (),
+                                           self.repair_max_conjuncts)
+            except native.Unsupported:  # one conjunct, or too many: no repair for this group
+                ex["repair_skipped"] = ex.get("repair_skipped", 0) + 1
+                continue
+            cts = TapeSet(columns)
+            cts.pool = ts.pool
+            cts.tapes = [Tape(t) for t in plan.tapes]
+            cts.flat = (plan.nodes, plan.tape_off, ts.pool.to_array())
+            try:
+                cct = self.compile(cts)
+            except native.Unsupported:
+                ex["repair_skipped"] = ex.get("repair_skipped", 0) + 1
+                continue
+            try:
+                ex["repair_tries"] = ex.get("repair_tries", 0) + 1
+                if set_leaf is None:
+                    set_leaf = guide.set_conjuncts()
+                tags = plan.set_ordinals(set_leaf)
+                if self.repairer is None:
+                    self.repairer = native.repair_open(self.ctx, self.repair_max_conjuncts, 1 << 16,
+                                                       256)
+                rep = self.repairer
+                if (self.assign2 is None or self.assign2.n_vars != assign.n_vars
+                        or self.assign2.capacity < K * per):
+                    if self.assign2 is not None:
+                        self.assign2.close()
+                    self.assign2 = self.ctx.assignments(assign.n_vars, K * per)
+                src, dst = assign, self.assign2
+                if src.capacity < K * per:  # the children ping-pong between the two buffers
+                    K = max(1, src.capacity // per)
+                native.repair_score(rep, cct, src, row_count=n_rows)
+                best_seen, stalled = None, 0
+                for it in range(self.repair_rounds):
+                    if time.perf_counter() - t0 > budget:
+                        break
+                    el = native.repair_select(rep, K, self.seed + it)
+                    best = int(el[0]["fail_count"])
+                    if it == 0 and best > self.repair_max_fail:
+                        ex["repair_far"] = ex.get("repair_far", 0) + 1
+                        break
+                    row = None
+                    if best == 0:
+                        # every conjunct of the group holds on the row: confirmed by the group's own
+                        # tape, the authority of an ordinary round
+                        r0 = int(el[0]["row"])
+                        fh, _, wrows = native.run_rows(self.ctx, ct, src, len(columns), tape_first=g,
+                                                       tape_count=1, row_first=r0, row_count=1,
+                                                       index_base=base - r0,
+                                                       mode=native.MODE_FIRST_HIT)
+                        if int(fh[0]) != native.NO_HIT:
+                            row = wrows[0]
+                            hit = int(fh[0])
+                    if row is None:
+                        if best_seen is not None and best >= best_seen:
+                            stalled += 1
+                            if stalled >= self.repair_stall:
+                                break
+                        else:
+                            best_seen, stalled = best, 0
+                        ex["repair_iters"] = ex.get("repair_iters", 0) + 1
+                        lr["repair"] += 1
+                        n_ch = len(el) * per
+                        native.repair_mutate(rep, src, dst, guide, tags, plan.col_off,
+                                             plan.cols_flat, per, seed=self.seed, global_base=base)
+                        fh, _, wrows = native.run_rows(self.ctx, ct, dst, len(columns), tape_first=g,
+                                                       tape_count=1, row_first=0, row_count=n_ch,
+                                                       index_base=base, mode=native.MODE_FIRST_HIT)
+                        st.rows += n_ch
+                        base += n_ch
+                        if int(fh[0]) != native.NO_HIT:
+                            row = wrows[0]
+                            hit = int(fh[0])
+                        else:
+                            native.repair_score(rep, cct, dst, row_count=n_ch)
+                            src, dst = dst, src
+                            continue
+                    raw = np.ascontiguousarray(row, dtype="<u4").tobytes()
+                    for c in group_cols[g]:
+                        values[columns[c]] = int.from_bytes(raw[32 * c:32 * c + 32], "little")
+                    solved[g] = True
+                    first_hit = hit if first_hit is None else min(first_hit, hit)
+                    ex["repair_hits"] = ex.get("repair_hits", 0) + 1
+                    break
+            finally:
+                cct.close()
+                st.add("repair", time.perf_counter() - tr)
+        return first_hit
 
 
 def newest_tape(nodes: np.ndarray, parent_len: int, hops: int = 0) -> Optional[np.ndarray]:

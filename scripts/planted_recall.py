@@ -22,6 +22,10 @@ answered the miss with M -- an upper bound on what learning z3's models gives, s
 a prefix need not satisfy the path's later constraints as M does.
 
 --fake runs on tests/fake_device.py (CPU; use small sizes).
+
+SIEVE_REPAIR=n turns the repair step on (Sieve.repair_rounds): its hits count in
+``recall`` and are reported apart as ``hit_repair``, with the repair counters.  With it off the
+summary is what it was before the repair step existed.
 """
 import json
 import os
@@ -76,6 +80,9 @@ def planted_value(m, ctx=None):
     return value_of
 
 
+REPAIR_STATS = ("tries", "hits", "iters", "far", "skipped")
+
+
 def run_family(s, family, n_paths, path_len, big=None, check=True, feedback=False):
     """Every prefix of n_paths planted paths in LASER order on sieve `s`.  Returns the summary
     and the list of missed (seed, prefix) pairs."""
@@ -87,6 +94,7 @@ def run_family(s, family, n_paths, path_len, big=None, check=True, feedback=Fals
     learnt0 = s.stats.extra.get("learnt", 0)
     k2t0 = s.stats.extra.get("keccak2_tries", 0)
     k2hits = 0
+    rep0 = {k: s.stats.extra.get("repair_" + k, 0) for k in REPAIR_STATS}
     for seed in range(n_paths):
         ctx, cs, m, kinds = planted_path(family, seed, path_len)
         nodes = [c.node for c in cs]
@@ -97,7 +105,7 @@ def run_family(s, family, n_paths, path_len, big=None, check=True, feedback=Fals
                 w = s.solve(ctx.b, nodes[:k], key=tuple(nodes[:k]))
                 dt = (time.perf_counter() - t0) * 1e3
                 if w is not None:
-                    kind = "hit_r%d" % w.rounds
+                    kind = "hit_repair" if w.repaired else "hit_r%d" % w.rounds
                     k2hits += bool(getattr(w.schema, "keccak_reads", False))
                     if check and not holds_original(ctx, cs[:k], w.schema, w.values):
                         bad.append((seed, k))
@@ -119,7 +127,7 @@ def run_family(s, family, n_paths, path_len, big=None, check=True, feedback=Fals
                 progress[kind + ("_r1_partial" if part else "_r1_none")] += 1
             times[kind].append(dt)
     n = sum(outcomes.values())
-    hits = outcomes["hit_r1"] + outcomes["hit_r2"]
+    hits = outcomes["hit_r1"] + outcomes["hit_r2"] + outcomes["hit_repair"]
     out = {
         "family": family, "paths": n_paths, "path_len": path_len, "queries": n,
         "recall": round(hits / max(n, 1), 4),
@@ -134,12 +142,19 @@ def run_family(s, family, n_paths, path_len, big=None, check=True, feedback=Fals
         "feedback": feedback, "learnt": s.stats.extra.get("learnt", 0) - learnt0,
         "first_round_progress": dict(progress),
         "by_newest_constraint": {
-            k: {"n": sum(c.values()), "recall": round((c["hit_r1"] + c["hit_r2"]) /
-                                                      max(sum(c.values()), 1), 4),
+            k: {"n": sum(c.values()), "recall": round((c["hit_r1"] + c["hit_r2"] + c["hit_repair"])
+                                                      / max(sum(c.values()), 1), 4),
                 "round2_only": c["hit_r2"], "miss": c["miss"]}
             for k, c in sorted(by_kind.items())},
         "ms": {k: _pct(v) for k, v in sorted(times.items())},
     }
+    if s.repair_rounds > 0:
+        ex = s.stats.extra
+        out["hit_repair"] = outcomes["hit_repair"]
+        out["repair"] = {"rounds": s.repair_rounds, "elites": s.repair_elites,
+                         "children": s.repair_children, "stall": s.repair_stall,
+                         "max_fail": s.repair_max_fail,
+                         **{k: ex.get("repair_" + k, 0) - rep0.get(k, 0) for k in REPAIR_STATS}}
     if big is not None and missed:
         rec = 0
         for seed, k in missed:
@@ -163,9 +178,9 @@ def main():
     if fake:
         import pytest
 
-        from tests import fake_device
+        from tests import repair_ref
 
-        fake_device.install(pytest.MonkeyPatch())
+        repair_ref.install(pytest.MonkeyPatch())  # tests/fake_device.py and the repair stand-in
     policy = next((a.split("=", 1)[1] for a in sys.argv if a.startswith("--round2=")), None)
     # the stand-in is slow: a budget that does not cut its rounds short
     s = (Sieve(rows=256, second_round=policy, budget_s=60.0) if fake

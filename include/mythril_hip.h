@@ -420,7 +420,8 @@ int32_t mh_eval_values(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape, const m
 
 /* Batched parity path (Model.eval, laser/smt/model.py:45-59, read in loops by the reference:
  * calldata.py:240-245 evaluates one byte term per call): the root values of the `n` listed tapes
- * at ONE row of `as`, out[8 * i + k] = limb k of tapes[i]'s root.  One kernel launch per
+ * at ONE row of `as`, out[8 * i + k] = limb k of tapes[i]'s root.  The list may be in any order
+ * and may repeat ids (each position gets its tape's value).  One kernel launch per
  * register-class variant among the listed tapes (usually one), one copy back, one sync.       */
 int32_t mh_eval_values_many(mh_ctx* ctx, const mh_tapeset* ts, const uint32_t* tapes, uint32_t n,
                             const mh_assign* as, uint64_t row, uint32_t* out /* [8*n] */);

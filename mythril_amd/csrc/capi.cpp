@@ -1426,8 +1426,14 @@ int32_t mh_eval_values_many(mh_ctx* ctx, const mh_tapeset* ts, const uint32_t* t
         if (!mh::variant_fits(v, as->stride)) return refuse_capacity(as->stride);
         by_var.push_back({v, i});
     }
-    std::stable_sort(by_var.begin(), by_var.end(),
-                     [](const auto& a, const auto& b) { return a.first < b.first; });
+    // by (variant, tape id, position): the kernel's chunk formation needs the ids of a launch
+    // ascending (a chunk is one contiguous range of the bucket's words, its end the last tape's);
+    // the caller's order comes back through .second below, a repeated id is evaluated again
+    std::sort(by_var.begin(), by_var.end(), [&](const auto& a, const auto& b) {
+        if (a.first != b.first) return a.first < b.first;
+        if (tapes[a.second] != tapes[b.second]) return tapes[a.second] < tapes[b.second];
+        return a.second < b.second;
+    });
     // device block: values [n][8], ids [n], first_hit / hit_count [top + 1] each (scratch: the
     // kernel's count-mode bookkeeping, indexed by tape id)
     const size_t n_words = (size_t)8 * n + n + 4 * ((size_t)top + 1) + 2;

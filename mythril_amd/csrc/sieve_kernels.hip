@@ -277,6 +277,8 @@ __device__ __forceinline__ void sieve_body(const KParams& p) {
         if (tid < (u32)kChunk) {
             // chunk formation by wave 0: the bucket's tapes are contiguous in the word array,
             // so the chunk is the longest prefix of the next kChunk tapes within kLdsInsns
+            // (precondition: a launch's ids ascend inside a bucket, buckets in word order; an id
+            // may repeat -- `end` then never decreases along the list and `fit` is a prefix)
             const u32 i = cb + tid;
             const bool in = i < n_ids;
             const u32 t = in ? tape_ids[i] : 0u;

@@ -158,6 +158,25 @@ class TapeFuzzer:
         return self.ts.add(self.b.finish(root))
 
 
+def tree_tape(ts, b, depth, salt, n_cols=3, compare=True):
+    """A complete binary expression tree over distinct 64-bit slices of the columns, compared
+    with a constant: depth + 3 registers (Sethi-Ullman, beside the three resident columns).
+    compare=False leaves the 64-bit tree itself as the root."""
+    ops = [Op.BVMUL, Op.BVADD, Op.BVXOR, Op.BVSUB]
+    cnt = [0]
+
+    def rec(d):
+        if d == 0:
+            i = cnt[0]
+            cnt[0] += 1
+            lo = (7 * i + salt) % 192
+            return b.op(Op.EXTRACT, b.var("v%d" % (i % n_cols), 256), imm0=lo + 63, imm1=lo)
+        return b.op(ops[(d + cnt[0]) % 4], rec(d - 1), rec(d - 1))
+
+    root = rec(depth)
+    return ts.add(b.finish(b.op(Op.BVULT, root, b.const(1 << 62, 64)) if compare else root))
+
+
 def assignment_soa(rng: random.Random, n_vars: int, rows: int) -> np.ndarray:
     soa = np.zeros((n_vars, 8, rows), dtype=np.uint32)
     for r in range(rows):

@@ -11,7 +11,7 @@ from mythril_amd.sieve import Sieve
 from mythril_amd.tape import Op, TapeSet
 from oracle import smt_eval as E
 from tests import repair_ref
-from tests.fuzz import TapeFuzzer, assignment_soa, soa_row
+from tests.fuzz import TapeFuzzer, assignment_soa, soa_row, tree_tape
 from tests.repair_cases import chain_query
 from tests.test_gpu_frontend import _random_guide
 from tests.test_reference_fixtures import holds_original
@@ -74,23 +74,6 @@ def scoring(gpu_ctx):
 
 def native_nr_class(n_regs):  # csrc/kernels.h nr_class
     return 0 if n_regs <= 7 else 1 if n_regs <= 9 else 2
-
-
-def tree_tape(ts, b, depth, salt):
-    """A complete binary expression tree over distinct 64-bit slices of the columns, compared
-    with a constant: depth + 3 registers (Sethi-Ullman, beside the three resident columns)."""
-    ops = [Op.BVMUL, Op.BVADD, Op.BVXOR, Op.BVSUB]
-    cnt = [0]
-
-    def rec(d):
-        if d == 0:
-            i = cnt[0]
-            cnt[0] += 1
-            lo = (7 * i + salt) % 192
-            return b.op(Op.EXTRACT, b.var("v%d" % (i % 3), 256), imm0=lo + 63, imm1=lo)
-        return b.op(ops[(d + cnt[0]) % 4], rec(d - 1), rec(d - 1))
-
-    return ts.add(b.finish(b.op(Op.BVULT, rec(depth), b.const(1 << 62, 64))))
 
 
 # conjunct counts across the interpreter's 64-tape LDS chunk, rows across the one-wave (<= 4096

@@ -62,6 +62,10 @@ struct Val {
 
 enum : uint32_t { LBL_SC_SKIP = 0xFFF0, LBL_SC_END = 0xFFF1 };  // tape-local labels
 
+// A conjunct is staged when its slice's hot path is at least this many VALU below its full cone
+// (emit_staged; DESIGN 5.1 has the A/B).
+constexpr uint32_t kStageMargin = 8;
+
 int top_bit(uint32_t m) { return m ? 31 - __builtin_clz(m) : -1; }
 uint32_t prefix_mask(uint32_t m) { int t = top_bit(m); return t < 0 ? 0u : ((2u << t) - 1u); }
 
@@ -76,7 +80,7 @@ public:
     TapeCode run();
 
 private:
-    const SsaTape& st_;
+    SsaTape st_;  // a copy: staging reorders the cones of staged conjuncts (plan_stages)
     const std::vector<uint32_t>& pool_;
     uint32_t n_vars_;
     Options opt_;
@@ -280,7 +284,25 @@ private:
     void op_mulmod(int d, const Val& X, const Val& Y, const Val& N);
     int scratch_ = -1;  // a virtual register past the tape's own (op_exp's products)
     void demand();
+    template <class F> void demand_rule(const SsaInsn& v, uint32_t dd, F&& D);
     void sc_check(const Val& v);
+    void emit_insn(int i, bool slice, bool no_check);
+    // ---- staged conjuncts (short-circuit builds, MH_JIT_STAGE > 0)
+    struct Stage { int first_e, ic, acc; };  // exclusive cone [first_e, ic), compare ic, chain acc
+    struct Slack { uint32_t lo = 0, hi = 0; };
+public:
+    int stage_ = 0;                          // level (0 = off)
+    const std::vector<uint8_t>* stage_skip_ = nullptr;  // conjunct vregs not to stage
+    std::vector<int> stage_rejected_;        // out: staged conjuncts that did not pay
+private:
+    std::vector<Stage> stages_;
+    std::vector<Slack> slack_;               // of the slice values (layer 3), by vreg
+    std::vector<uint8_t> slack_ok_;          // slice add/sub that may leave the carry-in open
+    bool in_slice_ = false;
+    void plan_stages();
+    void emit_staged(const Stage& sg);
+    void cmp32(uint16_t op, Limb x, Limb y);
+    bool stage_decide(const SsaInsn& c, int q, int acc);
     Val& out(int d) {
         Val& v = vals_[d];
         v = Val();
@@ -410,6 +432,28 @@ int Emitter::chain(bool sub, const Limb* a, const Limb* b, int top, Limb* res, u
 
 void Emitter::op_addsub(int d, const Val& A, const Val& B, bool sub) {
     const int top = top_bit(dem_[d]);
+    if (in_slice_ && slack_ok_[d]) {
+        // a slice that asks for the top limb alone, of a consumer that tolerates an open carry-in
+        // (emit_staged, layer 3): t = a7 +- b7 mod 2^32, one full-rate op; the true top limb is
+        // t + e, e in [-lo, hi] -- the operands' slacks, plus the carry (hi) or the borrow (lo)
+        const Limb x = A.l[7], y = B.l[7];
+        if (x.k == L_UNDEF || y.k == L_UNDEF) fail("internal: slice over an undemanded top limb");
+        Val& R = out(d);
+        if (x.is_c() && y.is_c()) {
+            R.l[7] = Limb::C(sub ? x.v - y.v : x.v + y.v);
+        } else {
+            const uint32_t dst = valloc();
+            if (!sub) {
+                if (y.is_r()) emit(M_V_ADD_U32, {V(dst), src(x), V(y.v)});
+                else emit(M_V_ADD_U32, {V(dst), src(y), V(x.v)});
+            } else {
+                if (y.is_r()) emit(M_V_SUB_U32, {V(dst), src(x), V(y.v)});        // x - y
+                else emit(M_V_SUBREV_U32, {V(dst), src(y), V(x.v)});              // x - y
+            }
+            R.l[7] = Limb::R(dst);
+        }
+        return;
+    }
     Val& R = out(d);
     if (top < 0) return;
     std::vector<uint32_t> tmp;
@@ -1385,83 +1429,84 @@ void Emitter::op_keccak(const SsaInsn& v, int cur) {
     }
 }
 
+template <class F>
+void Emitter::demand_rule(const SsaInsn& v, uint32_t dd, F&& D) {
+    const uint8_t op = v.op;
+    switch (op) {
+        case D_NOP: D(v.a, dd); break;
+        case D_ADD_R: case D_SUB_R: case D_RSUB_R: case D_MUL_R:
+            D(v.a, prefix_mask(dd));
+            D(v.b, prefix_mask(dd));
+            break;
+        case D_AND_R: case D_OR_R: case D_XOR_R: {
+            uint32_t ma = dd;
+            if (v.cidx >= 0) {
+                for (int k = 0; k < 8; ++k) {
+                    const uint32_t c = pool_[8ull * (uint32_t)v.cidx + k];
+                    if ((op == D_AND_R && c == 0) || (op == D_OR_R && c == ~0u))
+                        ma &= ~(1u << k);
+                }
+            }
+            D(v.a, ma);
+            D(v.b, dd);
+            break;
+        }
+        case D_ITE: D(v.b, dd); D(v.c, dd); break;
+        case D_EXP: case D_MULMOD:
+            D(v.a, 0xFF);
+            D(v.b, 0xFF);
+            D(v.c, 0xFF);
+            break;
+        case D_SHL_V: case D_LSHR_V: case D_ASHR_V:
+            D(v.a, 0xFF);
+            D(v.b, 0xFF);
+            break;
+        default:
+            if (op >= D_SHR0 && op <= D_SHR7) {
+                const uint32_t s = 32u * (op - D_SHR0) + (v.aux & 31u);
+                const uint32_t q = s >> 5, bsh = s & 31;
+                uint32_t m = 0;
+                for (int k = 0; k < 8; ++k)
+                    if ((dd >> k) & 1) {
+                        if (k + q < 8) m |= 1u << (k + q);
+                        if (bsh && k + q + 1 < 8) m |= 1u << (k + q + 1);
+                    }
+                D(v.a, m);
+            } else if (op >= D_SHL0 && op <= D_SHL7) {
+                const uint32_t p = op - D_SHL0, f = v.aux & 31u;
+                const uint32_t s = f ? 32u * p + 32u - f : 32u * (p + 1u);
+                if (s < 256) {
+                    const int q = (int)(s >> 5), bsh = (int)(s & 31);
+                    uint32_t m = 0;
+                    for (int k = 0; k < 8; ++k)
+                        if ((dd >> k) & 1) {
+                            if (k - q >= 0) m |= 1u << (k - q);
+                            if (bsh && k - q - 1 >= 0) m |= 1u << (k - q - 1);
+                        }
+                    D(v.a, m);
+                }
+            } else if ((op >= D_EQ_R && op <= D_SGE_C) ||
+                       (op >= D_UDIV_R && op <= D_SMOD_C)) {
+                D(v.a, 0xFF);
+                D(v.b, 0xFF);
+            } else if (op == D_KECCAK) {
+                D(v.a, 0xFF);
+                D(v.b, 0xFF);
+                D(v.c, 0xFF);
+            } else {  // Bool ops, constants
+                D(v.a, 0);
+            }
+            break;
+    }
+}
+
 void Emitter::demand() {
     const auto& code = st_.code;
     const int nv = st_.n_vregs;
     dem_.assign(nv, 0);
     if (st_.root >= 0) dem_[st_.root] = 0xFF;
     auto D = [&](int r, uint32_t m) { if (r >= 0) dem_[r] |= (uint8_t)m; };
-    for (size_t i = code.size(); i-- > 0;) {
-        const SsaInsn& v = code[i];
-        const uint32_t dd = dem_[v.d];
-        const uint8_t op = v.op;
-        switch (op) {
-            case D_NOP: D(v.a, dd); break;
-            case D_ADD_R: case D_SUB_R: case D_RSUB_R: case D_MUL_R:
-                D(v.a, prefix_mask(dd));
-                D(v.b, prefix_mask(dd));
-                break;
-            case D_AND_R: case D_OR_R: case D_XOR_R: {
-                uint32_t ma = dd;
-                if (v.cidx >= 0) {
-                    for (int k = 0; k < 8; ++k) {
-                        const uint32_t c = pool_[8ull * (uint32_t)v.cidx + k];
-                        if ((op == D_AND_R && c == 0) || (op == D_OR_R && c == ~0u))
-                            ma &= ~(1u << k);
-                    }
-                }
-                D(v.a, ma);
-                D(v.b, dd);
-                break;
-            }
-            case D_ITE: D(v.b, dd); D(v.c, dd); break;
-            case D_EXP: case D_MULMOD:
-                D(v.a, 0xFF);
-                D(v.b, 0xFF);
-                D(v.c, 0xFF);
-                break;
-            case D_SHL_V: case D_LSHR_V: case D_ASHR_V:
-                D(v.a, 0xFF);
-                D(v.b, 0xFF);
-                break;
-            default:
-                if (op >= D_SHR0 && op <= D_SHR7) {
-                    const uint32_t s = 32u * (op - D_SHR0) + (v.aux & 31u);
-                    const uint32_t q = s >> 5, bsh = s & 31;
-                    uint32_t m = 0;
-                    for (int k = 0; k < 8; ++k)
-                        if ((dd >> k) & 1) {
-                            if (k + q < 8) m |= 1u << (k + q);
-                            if (bsh && k + q + 1 < 8) m |= 1u << (k + q + 1);
-                        }
-                    D(v.a, m);
-                } else if (op >= D_SHL0 && op <= D_SHL7) {
-                    const uint32_t p = op - D_SHL0, f = v.aux & 31u;
-                    const uint32_t s = f ? 32u * p + 32u - f : 32u * (p + 1u);
-                    if (s < 256) {
-                        const int q = (int)(s >> 5), bsh = (int)(s & 31);
-                        uint32_t m = 0;
-                        for (int k = 0; k < 8; ++k)
-                            if ((dd >> k) & 1) {
-                                if (k - q >= 0) m |= 1u << (k - q);
-                                if (bsh && k - q - 1 >= 0) m |= 1u << (k - q - 1);
-                            }
-                        D(v.a, m);
-                    }
-                } else if ((op >= D_EQ_R && op <= D_SGE_C) ||
-                           (op >= D_UDIV_R && op <= D_SMOD_C)) {
-                    D(v.a, 0xFF);
-                    D(v.b, 0xFF);
-                } else if (op == D_KECCAK) {
-                    D(v.a, 0xFF);
-                    D(v.b, 0xFF);
-                    D(v.c, 0xFF);
-                } else {  // Bool ops, constants
-                    D(v.a, 0);
-                }
-                break;
-        }
-    }
+    for (size_t i = code.size(); i-- > 0;) demand_rule(code[i], dem_[code[i].d], D);
 }
 
 uint64_t Emitter::op_valu[256], Emitter::op_wide[256], Emitter::op_count[256];
@@ -1711,10 +1756,412 @@ bool schedule_impl(const SsaTape& st, const std::vector<uint32_t>& pool, uint32_
     return true;
 }
 
+// ---- staged conjuncts ----------------------------------------------------------------------
+// A conjunct of the root chain that is a 256-bit compare used by the chain's AND alone is decided,
+// where it can be, from one limb of each operand: limb 0 for ==, limb 7 for the ordered compares.
+// Its exclusive cone E -- the not yet computed instructions of its operand cone whose every use
+// lies in E or is the compare -- is first emitted under that slice demand into temporaries; the
+// decision yields a per-lane value and a per-lane "undecided" mask; when no live lane (the
+// conjunction so far and s[30:31]) is undecided the value is the conjunct and a uniform branch
+// skips the rest; else E is emitted at full demand with today's compare.  Both paths leave the
+// same registers: the slice's temporaries are dead before the branch, every value of E is dead
+// after the compare, and the result's SGPR pair is allocated before the split.
+//
+// plan_stages finds the candidates and moves, inside the run of instructions scheduled in front of
+// each, those used by later conjuncts as well (emitted in full first, as ever) before E.
+namespace {
+bool is_compare(uint8_t op) { return op >= D_EQ_R && op <= D_SGE_C; }
+bool sliceable(uint8_t op) {
+    return op == D_NOP || op == D_LOADC || op == D_ADD_R || op == D_SUB_R || op == D_RSUB_R ||
+           op == D_AND_R || op == D_OR_R || op == D_XOR_R || op == D_ITE || op == D_MUL_R ||
+           (op >= D_SHR0 && op <= D_SHL7) || is_compare(op) || (op >= D_BAND && op <= D_FALSE) ||
+           op == D_BITE;
+}
+}  // namespace
+
+void Emitter::plan_stages() {
+    const std::vector<SsaInsn> code = st_.code;
+    const int n = (int)code.size(), nv = st_.n_vregs;
+    std::vector<std::vector<int>> users(nv);
+    for (int i = 0; i < n; ++i)
+        for (int r : {code[i].a, code[i].b, code[i].c})
+            if (r >= 0 && r < nv) users[r].push_back(i);
+    std::vector<SsaInsn> out;
+    out.reserve(code.size());
+    std::vector<char> excl(n, 0);
+    bool seen_first = false;
+    int start = 0;
+    for (int i = 0; i < n; ++i) {
+        const SsaInsn& v = code[i];
+        if (v.d < 0 || v.d >= nv) return;
+        const bool first = !seen_first && (*check_)[v.d];
+        const bool band = seen_first && v.op == D_BAND && ((*check_)[v.d] || v.d == st_.root);
+        if (!first && !band) continue;
+        seen_first = true;
+        const int ic = first ? i : i - 1;
+        bool cand = ic >= start && is_compare(code[ic].op) && users[code[ic].d].size() == 1 &&
+                    (first || code[ic].d == v.b) && code[ic].d != st_.root &&
+                    !(stage_skip_ && (*stage_skip_)[code[ic].d]);
+        if (cand && code[ic].op != D_EQ_R && stage_ < 2) cand = false;
+        bool any = false;
+        if (cand) {
+            for (int j = ic - 1; j >= start; --j) {
+                const int d = code[j].d;
+                bool ok = sliceable(code[j].op) && d != st_.root && d >= st_.n_pinned;
+                for (int u : users[d]) ok = ok && (u == ic || (u >= start && u < ic && excl[u]));
+                excl[j] = ok;
+                any |= ok;
+            }
+        }
+        if (cand && any) {
+            for (int j = start; j < ic; ++j)
+                if (!excl[j]) out.push_back(code[j]);
+            Stage sg;
+            sg.first_e = (int)out.size();
+            for (int j = start; j < ic; ++j)
+                if (excl[j]) out.push_back(code[j]);
+            sg.ic = (int)out.size();
+            sg.acc = first ? -1 : v.a;
+            out.push_back(code[ic]);
+            stages_.push_back(sg);
+        } else {
+            for (int j = start; j <= ic; ++j) out.push_back(code[j]);
+        }
+        if (!first) out.push_back(code[i]);
+        start = i + 1;
+    }
+    for (int j = start; j < n; ++j) out.push_back(code[j]);
+    st_.code.swap(out);
+}
+
+// v_cmp_<op> vcc, x, y (x may be a constant; a constant y swaps the operands)
+void Emitter::cmp32(uint16_t op, Limb x, Limb y) {
+    if (y.is_c() && !x.is_c()) {
+        const uint16_t rev = op == M_V_CMP_LT ? M_V_CMP_GT
+                           : op == M_V_CMP_LT_I32 ? M_V_CMP_GT_I32 : op;
+        emit(rev, {VCC(), IMM(y.v), V(x.v)});
+    } else {
+        emit(op, {VCC(), src(x), V(y.v)});
+    }
+}
+
+// The decision of staged compare c from its operands' slice values.  Leaves the live undecided
+// lanes in pair q and in SCC whether there is one; for an ordered compare the deciding compare is
+// emitted by the caller's layout (see emit_staged).  Returns false when the slices cannot decide.
+bool Emitter::stage_decide(const SsaInsn& c, int q, int acc) {
+    const Val A0 = val(c.a);
+    const Val B0 = c.cidx >= 0 ? const_val(c.cidx) : val(c.b);
+    auto live = [&](Opnd und) {  // q = und & live lanes, SCC = any
+        if (acc >= 0 && val(acc).bconst < 0) {
+            emit(M_S_AND_B64, {P(q), und, P(val(acc).pair)});
+            emit(M_S_AND_B64, {P(q), P(q), S(S_VALID, 2)});
+        } else {
+            emit(M_S_AND_B64, {P(q), und, S(S_VALID, 2)});
+        }
+    };
+    if (c.op == D_EQ_R) {
+        // lanes whose low limbs differ are decided false, the others are undecided
+        Limb x = A0.l[0], y = B0.l[0];
+        if (x.k == L_UNDEF || y.k == L_UNDEF) return false;
+        if (x.is_c() && y.is_c()) return false;
+        if (x.is_r() && y.is_r() && x.v == y.v) return false;
+        if (!y.is_r()) std::swap(x, y);
+        emit(M_V_CMP_EQ, {VCC(), src(x), V(y.v)});
+        live(VCC());
+        return true;
+    }
+    const uint8_t k = (uint8_t)((c.op - D_ULT_R) >> 1);  // ult ugt ule uge slt sgt sle sge
+    const bool swap = (k & 3) == 1 || (k & 3) == 2, signed_ = k >= 4;  // ugt, ule: B < A
+    const Val& A = swap ? B0 : A0;
+    const Val& B = swap ? A0 : B0;
+    const int ra = swap ? (c.cidx >= 0 ? -1 : c.b) : c.a, rb = swap ? c.a : (c.cidx >= 0 ? -1 : c.b);
+    const Limb x = A.l[7], y = B.l[7];
+    if (x.k == L_UNDEF || y.k == L_UNDEF) return false;
+    if (x.is_c() && y.is_c()) return false;
+    if (x.is_r() && y.is_r() && x.v == y.v) return false;
+    const Slack sx = ra >= 0 ? slack_[ra] : Slack(), sy = rb >= 0 ? slack_[rb] : Slack();
+    const uint32_t D = sx.lo + sx.hi + sy.lo + sy.hi;
+    const uint32_t bias = signed_ ? 0x80000000u : 0u;
+    std::vector<uint32_t> tmp;
+    if (D == 0) {
+        // the top limbs are exact: lanes where they are equal are undecided
+        cmp32(M_V_CMP_EQ, x, y);
+        live(VCC());
+    } else {
+        if (D > 64) return false;
+        // the true top limbs are X' + eX, Y' + eY (X' = x biased for the signed order, which
+        // commutes with + e): decided when neither can wrap and |X' - Y'| > D
+        for (int s = 0; s < 2; ++s) {
+            const Limb l = s ? y : x;
+            const Slack sl = s ? sy : sx;
+            if (!l.is_c()) continue;
+            const uint32_t v = l.v ^ bias;
+            if (v < sl.lo || v > 0xFFFFFFFFu - sl.hi) return false;
+        }
+        // undecided: (X' - Y' + D) mod 2^32 <= 2 D
+        const uint32_t e = valloc();
+        tmp.push_back(e);
+        if (y.is_c()) {
+            emit(M_V_ADD_U32, {V(e), IMM(D - y.v), V(x.v)});
+        } else if (x.is_c()) {
+            emit(M_V_SUB_U32, {V(e), IMM(x.v + D), V(y.v)});
+        } else {
+            emit(M_V_SUB_U32, {V(e), V(x.v), V(y.v)});
+            emit(M_V_ADD_U32, {V(e), IMM(D), V(e)});
+        }
+        emit(M_V_CMP_GT, {VCC(), IMM(2 * D + 1), V(e)});
+        bool in_q = false;
+        for (int s = 0; s < 2; ++s) {
+            const Limb l = s ? y : x;
+            const Slack sl = s ? sy : sx;
+            if (l.is_c() || sl.lo + sl.hi == 0) continue;
+            // out of [lo, 2^32 - 1 - hi]: (X' - lo) mod 2^32 > 2^32 - 1 - hi - lo
+            if (!in_q) { emit(M_S_MOV_B64, {P(q), VCC()}); in_q = true; }
+            emit(M_V_ADD_U32, {V(e), IMM(bias - sl.lo), V(l.v)});
+            emit(M_V_CMP_LT, {VCC(), IMM(0xFFFFFFFFu - sl.hi - sl.lo), V(e)});
+            emit(M_S_OR_B64, {P(q), P(q), VCC()});
+        }
+        live(in_q ? P(q) : VCC());
+    }
+    free_tmp(tmp);
+    return true;
+}
+
+void Emitter::emit_staged(const Stage& sg) {
+    const SsaInsn& c = st_.code[sg.ic];
+    const int nv = st_.n_vregs;
+    const bool eq = c.op == D_EQ_R;
+    const int q = palloc();  // the conjunct's pair on both paths
+    // 1. slice demand over E, by demand()'s rules; exact[r]: some consumer needs limb 7 exactly
+    std::vector<uint8_t> sd(nv, 0), exact(nv, 0);
+    auto ask = [&](int r, uint32_t m, bool ex) {
+        if (r < 0 || r >= nv) return;
+        sd[r] |= (uint8_t)m;
+        if (ex && m) exact[r] = 1;
+    };
+    const bool open_carry = stage_ >= 3 && !eq;
+    ask(c.a, eq ? 0x01u : 0x80u, !open_carry);
+    if (c.cidx < 0) ask(c.b, eq ? 0x01u : 0x80u, !open_carry);
+    slack_ok_.assign(nv, 0);
+    for (int j = sg.ic - 1; j >= sg.first_e; --j) {
+        const SsaInsn& v = st_.code[j];
+        const uint32_t dd = sd[v.d];
+        const bool ex = exact[v.d] != 0;
+        if (open_carry && !ex && dd == 0x80u &&
+            (v.op == D_ADD_R || v.op == D_SUB_R || v.op == D_RSUB_R)) {
+            slack_ok_[v.d] = 1;
+            ask(v.a, 0x80u, false);
+            if (v.cidx < 0) ask(v.b, 0x80u, false);
+        } else if (v.op == D_NOP) {
+            ask(v.a, dd, ex);
+        } else if (v.op == D_ITE) {
+            ask(v.b, dd, ex);
+            ask(v.c, dd, ex);
+        } else {
+            demand_rule(v, dd, [&](int r, uint32_t m) { ask(r, m, true); });
+        }
+    }
+    // 2. the slice, into temporaries
+    const uint32_t hot0 = n_valu_ - n_valu_cold_;
+    std::vector<uint8_t> saved(sg.ic - sg.first_e);
+    slack_.assign(nv, Slack());
+    in_slice_ = true;
+    for (int j = sg.first_e; j < sg.ic; ++j) {
+        const SsaInsn& v = st_.code[j];
+        saved[j - sg.first_e] = dem_[v.d];
+        dem_[v.d] = sd[v.d];
+        const bool is_val = !(is_compare(v.op) || (v.op >= D_BAND && v.op <= D_FALSE) ||
+                              v.op == D_BITE);
+        if (is_val && sd[v.d] == 0) {  // nobody reads a limb of it
+            out(v.d);
+            continue;
+        }
+        emit_insn(j, true, true);
+        const Slack a = v.a >= 0 ? slack_[v.a] : Slack();
+        const Slack b = v.cidx < 0 && v.b >= 0 ? slack_[v.b] : Slack();
+        Slack r;
+        if (slack_ok_[v.d]) {
+            if (v.op == D_ADD_R) { r.lo = a.lo + b.lo; r.hi = a.hi + b.hi + 1; }
+            else if (v.op == D_SUB_R) { r.lo = a.lo + b.hi + 1; r.hi = a.hi + b.lo; }
+            else { r.lo = b.lo + a.hi + 1; r.hi = b.hi + a.lo; }  // y - a
+        } else if (v.op == D_NOP) {
+            r = a;
+        } else if (v.op == D_ITE) {
+            const Slack t = slack_[v.b], e = slack_[v.c];
+            r.lo = std::max(t.lo, e.lo);
+            r.hi = std::max(t.hi, e.hi);
+        }
+        slack_[v.d] = r;
+    }
+    in_slice_ = false;
+    // 3. the decision
+    cur_op_ = c.op;
+    const bool decided = stage_decide(c, q, sg.acc);
+    uint32_t l_cold = 0, l_join = 0;
+    if (decided) {
+        l_join = next_lbl_++;
+        if (eq) {
+            // no live lane undecided: false in every lane that matters, and q is 0
+            emit(M_S_CBRANCH_SCC0, {LBL(l_join)});
+        } else {
+            l_cold = next_lbl_++;
+            emit(M_S_CBRANCH_SCC1, {LBL(l_cold)});
+            const uint8_t k = (uint8_t)((c.op - D_ULT_R) >> 1);
+            const bool swap = (k & 3) == 1 || (k & 3) == 2, negate = (k & 3) >= 2, signed_ = k >= 4;
+            const Val A0 = val(c.a);
+            const Val B0 = c.cidx >= 0 ? const_val(c.cidx) : val(c.b);
+            const Limb x = (swap ? B0 : A0).l[7], y = (swap ? A0 : B0).l[7];
+            cmp32(signed_ ? M_V_CMP_LT_I32 : M_V_CMP_LT, x, y);
+            emit(negate ? M_S_NOT_B64 : M_S_MOV_B64, {P(q), VCC()});
+            emit(M_S_BRANCH, {LBL(l_join)});
+            emit(M_LABEL, {LBL(l_cold)});
+        }
+    }
+    const uint32_t hot = (n_valu_ - n_valu_cold_) - hot0;
+    // the slice's temporaries are dead here, on both paths
+    for (int j = sg.first_e; j < sg.ic; ++j) {
+        const SsaInsn& v = st_.code[j];
+        if (vals_[v.d].defined) release(vals_[v.d]);
+        vals_[v.d] = Val();
+        dem_[v.d] = saved[j - sg.first_e];
+    }
+    // 4. the cold path: E at full demand and the full compare, into the same pair
+    const uint32_t full0 = n_valu_ - n_valu_cold_;
+    for (int j = sg.first_e; j <= sg.ic; ++j) emit_insn(j, false, true);
+    const uint32_t full = (n_valu_ - n_valu_cold_) - full0;
+    n_valu_cold_ += full;  // the scheduler's cost model prices the hot path only
+    const Val r = vals_[c.d];
+    cur_op_ = c.op;
+    if (r.bconst >= 0) {
+        emit(M_S_MOV_B64, {P(q), IMM(r.bconst ? 0xFFFFFFFFu : 0u)});
+    } else {
+        emit(M_S_MOV_B64, {P(q), P(r.pair)});
+        release(r);
+    }
+    if (decided) emit(M_LABEL, {LBL(l_join)});
+    vals_[c.d] = bool_mask(q);
+    if (!decided || hot + kStageMargin > full) stage_rejected_.push_back(c.d);
+    if (check_ && (*check_)[c.d]) sc_check(vals_[c.d]);
+}
+
+// One SSA instruction.  slice: emitted under a slice demand into temporaries (emit_staged) --
+// operands are not released and nothing is tested.
+void Emitter::emit_insn(int i, bool slice, bool no_check) {
+    const SsaInsn& v = st_.code[i];
+    const uint8_t op = v.op;
+    cur_op_ = op;
+    const uint32_t valu_before = n_valu_, cold_before = n_valu_cold_;
+    ++op_count[op];
+    auto Y = [&]() -> Val { return v.cidx >= 0 ? const_val(v.cidx) : val(v.b); };
+    switch (op) {
+        case D_NOP: {
+            const Val& a = val(v.a);
+            retain(a);
+            vals_[v.d] = a;
+            break;
+        }
+        case D_LOADC: vals_[v.d] = const_val(v.cidx); break;
+        case D_LOADVAR: {  // a column not pinned: the demanded limbs, one load each
+            const uint32_t dm = dem_[v.d];
+            Val& R = out(v.d);
+            for (int k = 0; k < 8; ++k)
+                if ((dm >> k) & 1u) {
+                    const uint32_t r = valloc();
+                    emit(M_LOADCOL, {V(r), IMM(8u * v.aux + (uint32_t)k)});
+                    R.l[k] = Limb::R(r);
+                }
+            if (dm) emit(M_S_WAITCNT_VM, {IMM(0)});
+            break;
+        }
+        case D_TRUE: vals_[v.d] = bool_const(true); break;
+        case D_FALSE: vals_[v.d] = bool_const(false); break;
+        case D_ADD_R: op_addsub(v.d, val(v.a), Y(), false); break;
+        case D_SUB_R: op_addsub(v.d, val(v.a), Y(), true); break;
+        case D_RSUB_R: op_addsub(v.d, Y(), val(v.a), true); break;
+        case D_AND_R: op_logic(v.d, val(v.a), Y(), 0); break;
+        case D_OR_R: op_logic(v.d, val(v.a), Y(), 1); break;
+        case D_XOR_R: op_logic(v.d, val(v.a), Y(), 2); break;
+        case D_EQ_R: vals_[v.d] = op_eq(val(v.a), Y()); break;
+        case D_ULT_R: vals_[v.d] = op_ult(val(v.a), Y(), false, false); break;
+        case D_UGE_R: vals_[v.d] = op_ult(val(v.a), Y(), false, true); break;
+        case D_UGT_R: vals_[v.d] = op_ult(Y(), val(v.a), false, false); break;
+        case D_ULE_R: vals_[v.d] = op_ult(Y(), val(v.a), false, true); break;
+        case D_SLT_R: vals_[v.d] = op_ult(val(v.a), Y(), true, false); break;
+        case D_SGE_R: vals_[v.d] = op_ult(val(v.a), Y(), true, true); break;
+        case D_SGT_R: vals_[v.d] = op_ult(Y(), val(v.a), true, false); break;
+        case D_SLE_R: vals_[v.d] = op_ult(Y(), val(v.a), true, true); break;
+        case D_BAND: case D_BOR: case D_BXOR: case D_BEQ:
+            vals_[v.d] = op_bool2(op, val(v.a), val(v.b));
+            break;
+        case D_BNOT: {
+            const Val& a = val(v.a);
+            if (a.bconst >= 0) {
+                vals_[v.d] = bool_const(!a.bconst);
+            } else {
+                const int p = palloc();
+                emit(M_S_NOT_B64, {P(p), P(a.pair)});
+                vals_[v.d] = bool_mask(p);
+            }
+            break;
+        }
+        case D_ITE: op_ite(v.d, val(v.a), val(v.b), val(v.c)); break;
+        case D_BITE: vals_[v.d] = op_bite(val(v.a), val(v.b), val(v.c)); break;
+        case D_MUL_R: op_mul(v.d, val(v.a), Y()); break;
+        case D_SHL_V: case D_LSHR_V: case D_ASHR_V:
+            op_vshift(v.d, val(v.a), val(v.b), op);
+            break;
+        case D_UDIV_R: case D_UREM_R: case D_SDIV_R: case D_SREM_R: case D_SMOD_R:
+            op_div(v.d, v.a, v.b, v.cidx, (uint32_t)(op - D_UDIV_R) >> 1, i);
+            break;
+        case D_KECCAK: op_keccak(v, i); break;
+        case D_EXP: op_exp(v.d, val(v.a), Y()); break;
+        case D_MULMOD: op_mulmod(v.d, val(v.a), val(v.b), val(v.c)); break;
+        default:
+            if (op >= D_SHR0 && op <= D_SHR7) {
+                const uint32_t s = 32u * (op - D_SHR0) + (v.aux & 31u);
+                if (s == 0) { const Val& a = val(v.a); retain(a); vals_[v.d] = a; }
+                else op_shr(v.d, val(v.a), s);
+            } else if (op >= D_SHL0 && op <= D_SHL7) {
+                const uint32_t p = op - D_SHL0, f = v.aux & 31u;
+                const uint32_t s = f ? 32u * p + 32u - f : 32u * (p + 1u);
+                if (s >= 256) {
+                    Val& R = out(v.d);
+                    for (int k = 0; k < 8; ++k) R.l[k] = Limb::C(0);
+                } else {
+                    op_shl(v.d, val(v.a), s);
+                }
+            } else {
+                fail("op " + std::to_string(op) + " not in the JIT");
+            }
+            break;
+    }
+    vals_[v.d].defined = true;
+    // operands whose last use this was
+    int seen[3] = {-1, -1, -1};
+    int ns = 0;
+    for (int r : {v.a, v.b, v.c}) {
+        if (slice || r < 0 || last_[r] != i) continue;
+        bool dup = false;
+        for (int j = 0; j < ns; ++j) dup |= seen[j] == r;
+        if (dup) continue;
+        seen[ns++] = r;
+        release(vals_[r]);
+    }
+    if (check_ && !slice && !no_check && (*check_)[v.d]) sc_check(vals_[v.d]);
+    if (insn_cost_ && !slice) {
+        // a division-family call runs ~90 VALU in the subroutine (tests/tools/jit_mix.py)
+        const bool call = op >= D_UDIV_R && op <= D_SMOD_C;
+        (*insn_cost_)[i] = (double)(n_valu_ - valu_before) -
+                           (double)(n_valu_cold_ - cold_before) + (call ? 90.0 : 0.0) +
+                           (op == D_KECCAK ? 7000.0 : 0.0);
+    }
+}
+
 TapeCode Emitter::run() {
     TapeCode tc;
     tc.alg_ops = st_.alg_ops;
     try {
+        if (check_ && stage_ > 0) plan_stages();
         const auto& code = st_.code;
         const int nv = st_.n_vregs;
         if (insn_cost_) insn_cost_->assign(code.size(), 0.0);
@@ -1756,115 +2203,14 @@ TapeCode Emitter::run() {
         vals_.push_back(Val());
         last_.push_back(-1);
         dem_.push_back(0xFF);
+        size_t si = 0;
         for (int i = 0; i < (int)code.size(); ++i) {
-            const SsaInsn& v = code[i];
-            const uint8_t op = v.op;
-            cur_op_ = op;
-            const uint32_t valu_before = n_valu_, cold_before = n_valu_cold_;
-            ++op_count[op];
-            auto Y = [&]() -> Val { return v.cidx >= 0 ? const_val(v.cidx) : val(v.b); };
-            switch (op) {
-                case D_NOP: {
-                    const Val& a = val(v.a);
-                    retain(a);
-                    vals_[v.d] = a;
-                    break;
-                }
-                case D_LOADC: vals_[v.d] = const_val(v.cidx); break;
-                case D_LOADVAR: {  // a column not pinned: the demanded limbs, one load each
-                    const uint32_t dm = dem_[v.d];
-                    Val& R = out(v.d);
-                    for (int k = 0; k < 8; ++k)
-                        if ((dm >> k) & 1u) {
-                            const uint32_t r = valloc();
-                            emit(M_LOADCOL, {V(r), IMM(8u * v.aux + (uint32_t)k)});
-                            R.l[k] = Limb::R(r);
-                        }
-                    if (dm) emit(M_S_WAITCNT_VM, {IMM(0)});
-                    break;
-                }
-                case D_TRUE: vals_[v.d] = bool_const(true); break;
-                case D_FALSE: vals_[v.d] = bool_const(false); break;
-                case D_ADD_R: op_addsub(v.d, val(v.a), Y(), false); break;
-                case D_SUB_R: op_addsub(v.d, val(v.a), Y(), true); break;
-                case D_RSUB_R: op_addsub(v.d, Y(), val(v.a), true); break;
-                case D_AND_R: op_logic(v.d, val(v.a), Y(), 0); break;
-                case D_OR_R: op_logic(v.d, val(v.a), Y(), 1); break;
-                case D_XOR_R: op_logic(v.d, val(v.a), Y(), 2); break;
-                case D_EQ_R: vals_[v.d] = op_eq(val(v.a), Y()); break;
-                case D_ULT_R: vals_[v.d] = op_ult(val(v.a), Y(), false, false); break;
-                case D_UGE_R: vals_[v.d] = op_ult(val(v.a), Y(), false, true); break;
-                case D_UGT_R: vals_[v.d] = op_ult(Y(), val(v.a), false, false); break;
-                case D_ULE_R: vals_[v.d] = op_ult(Y(), val(v.a), false, true); break;
-                case D_SLT_R: vals_[v.d] = op_ult(val(v.a), Y(), true, false); break;
-                case D_SGE_R: vals_[v.d] = op_ult(val(v.a), Y(), true, true); break;
-                case D_SGT_R: vals_[v.d] = op_ult(Y(), val(v.a), true, false); break;
-                case D_SLE_R: vals_[v.d] = op_ult(Y(), val(v.a), true, true); break;
-                case D_BAND: case D_BOR: case D_BXOR: case D_BEQ:
-                    vals_[v.d] = op_bool2(op, val(v.a), val(v.b));
-                    break;
-                case D_BNOT: {
-                    const Val& a = val(v.a);
-                    if (a.bconst >= 0) {
-                        vals_[v.d] = bool_const(!a.bconst);
-                    } else {
-                        const int p = palloc();
-                        emit(M_S_NOT_B64, {P(p), P(a.pair)});
-                        vals_[v.d] = bool_mask(p);
-                    }
-                    break;
-                }
-                case D_ITE: op_ite(v.d, val(v.a), val(v.b), val(v.c)); break;
-                case D_BITE: vals_[v.d] = op_bite(val(v.a), val(v.b), val(v.c)); break;
-                case D_MUL_R: op_mul(v.d, val(v.a), Y()); break;
-                case D_SHL_V: case D_LSHR_V: case D_ASHR_V:
-                    op_vshift(v.d, val(v.a), val(v.b), op);
-                    break;
-                case D_UDIV_R: case D_UREM_R: case D_SDIV_R: case D_SREM_R: case D_SMOD_R:
-                    op_div(v.d, v.a, v.b, v.cidx, (uint32_t)(op - D_UDIV_R) >> 1, i);
-                    break;
-                case D_KECCAK: op_keccak(v, i); break;
-                case D_EXP: op_exp(v.d, val(v.a), Y()); break;
-                case D_MULMOD: op_mulmod(v.d, val(v.a), val(v.b), val(v.c)); break;
-                default:
-                    if (op >= D_SHR0 && op <= D_SHR7) {
-                        const uint32_t s = 32u * (op - D_SHR0) + (v.aux & 31u);
-                        if (s == 0) { const Val& a = val(v.a); retain(a); vals_[v.d] = a; }
-                        else op_shr(v.d, val(v.a), s);
-                    } else if (op >= D_SHL0 && op <= D_SHL7) {
-                        const uint32_t p = op - D_SHL0, f = v.aux & 31u;
-                        const uint32_t s = f ? 32u * p + 32u - f : 32u * (p + 1u);
-                        if (s >= 256) {
-                            Val& R = out(v.d);
-                            for (int k = 0; k < 8; ++k) R.l[k] = Limb::C(0);
-                        } else {
-                            op_shl(v.d, val(v.a), s);
-                        }
-                    } else {
-                        fail("op " + std::to_string(op) + " not in the JIT");
-                    }
-                    break;
+            if (si < stages_.size() && stages_[si].first_e == i) {
+                emit_staged(stages_[si]);
+                i = stages_[si++].ic;
+                continue;
             }
-            vals_[v.d].defined = true;
-            // operands whose last use this was
-            int seen[3] = {-1, -1, -1};
-            int ns = 0;
-            for (int r : {v.a, v.b, v.c}) {
-                if (r < 0 || last_[r] != i) continue;
-                bool dup = false;
-                for (int j = 0; j < ns; ++j) dup |= seen[j] == r;
-                if (dup) continue;
-                seen[ns++] = r;
-                release(vals_[r]);
-            }
-            if (check_ && (*check_)[v.d]) sc_check(vals_[v.d]);
-            if (insn_cost_) {
-                // a division-family call runs ~90 VALU in the subroutine (tests/tools/jit_mix.py)
-                const bool call = op >= D_UDIV_R && op <= D_SMOD_C;
-                (*insn_cost_)[i] = (double)(n_valu_ - valu_before) -
-                                   (double)(n_valu_cold_ - cold_before) + (call ? 90.0 : 0.0) +
-                                   (op == D_KECCAK ? 7000.0 : 0.0);
-            }
+            emit_insn(i, false, false);
         }
         // root
         const Val& root = val(st_.root);
@@ -3154,6 +3500,8 @@ bool build_tapeset(const mh_node* nodes, const uint64_t* offs, uint32_t n_tapes,
                    const Options& opt, uint32_t threads, std::vector<Built>& out,
                    BuildStats& stats, std::string& err) {
     threads = std::max<uint32_t>(1, std::min<uint32_t>(threads, (n_tapes + 63) / 64));
+    Options eopt = opt;
+    if (values) eopt.stage = 0;  // the parity path keeps the plain code
     out.clear();
     stats.jitted.assign(n_tapes, 0);
     stats.why.assign(n_tapes, std::string());
@@ -3209,7 +3557,7 @@ bool build_tapeset(const mh_node* nodes, const uint64_t* offs, uint32_t n_tapes,
         const uint32_t hi = (uint32_t)((uint64_t)n_tapes * (s + 1) / threads);
         std::vector<uint32_t> list;
         for (uint32_t t = lo; t < hi; ++t) list.push_back(t);
-        emit_list(list, opt, slices[s], true);
+        emit_list(list, eopt, slices[s], true);
     };
     {
         std::vector<std::thread> pool;
@@ -3224,7 +3572,7 @@ bool build_tapeset(const mh_node* nodes, const uint64_t* offs, uint32_t n_tapes,
         big.insert(big.end(), slices[s].over.begin(), slices[s].over.end());
     const uint32_t big_budget = std::max(opt.max_vgpr, opt.max_vgpr_keccak);
     if (!big.empty() && big_budget > opt.max_vgpr) {
-        Options o2 = opt;
+        Options o2 = eopt;
         o2.max_vgpr = big_budget;
         emit_list(big, o2, slices[threads], false);
     }
@@ -3395,6 +3743,13 @@ uint32_t coalesce_div_moves(std::vector<MI>& code) {
 
 static std::atomic<uint64_t> g_sc_fallbacks{0};
 
+// Staged conjuncts (emit_staged): MH_JIT_STAGE = 0 off, 1 == conjuncts, 2 + ordered compares from
+// exact top limbs, 3 + add / sub with the carry-in left open.
+static int stage_level() {
+    const char* e = std::getenv("MH_JIT_STAGE");  // read per tape: tests switch it in-process
+    return e ? std::min(3, std::max(0, atoi(e))) : 3;
+}
+
 uint64_t sc_fallbacks(bool reset) {
     return reset ? g_sc_fallbacks.exchange(0) : g_sc_fallbacks.load();
 }
@@ -3420,6 +3775,23 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
         SsaTape sc;
         std::vector<uint8_t> check;
         if (schedule_conjuncts(st, pool, opt.sample_rows, tc0.ok ? &cost : nullptr, sc, check)) {
+            const int level = opt.stage >= 0 ? opt.stage : stage_level();
+            if (level > 0) {
+                // staged conjuncts: a first emission prices every candidate (its slice's hot path
+                // against its full cone), a second keeps those that pay
+                Emitter e2(sc, pool, n_vars, opt, &check);
+                e2.stage_ = level;
+                TapeCode tc = e2.run();
+                if (tc.ok && !e2.stage_rejected_.empty()) {
+                    std::vector<uint8_t> skip((size_t)sc.n_vregs, 0);
+                    for (int d : e2.stage_rejected_) skip[(size_t)d] = 1;
+                    Emitter e3(sc, pool, n_vars, opt, &check);
+                    e3.stage_ = level;
+                    e3.stage_skip_ = &skip;
+                    tc = e3.run();
+                }
+                if (tc.ok) return tc;  // else (register pressure of the slices): unstaged
+            }
             Emitter e2(sc, pool, n_vars, opt, &check);
             TapeCode tc = e2.run();
             if (tc.ok) return tc;  // else (register pressure of the new order): source order

@@ -167,6 +167,9 @@ struct Options {
     // Producers of division operands write the subroutine's input registers directly where the
     // copy at the call site would be the value's last use (coalesce_div_moves).
     bool coalesce = true;
+    // Staged conjuncts of short-circuit builds (jit.cpp emit_staged): the level, 0 = off;
+    // -1 = MH_JIT_STAGE, or the default level.
+    int stage = -1;
     // Assemble the module texts (comgr).  false: emission and module text only -- enough for the
     // code id (Built::text_hash), with no assembler and no device.
     bool assemble = true;

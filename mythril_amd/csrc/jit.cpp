@@ -104,8 +104,10 @@ private:
     bool uses_lds_ = false;
     bool calls_kec_ = false;
     int cur_op_ = -1;  // SSA op being emitted (diagnostic attribution)
+    int live_vreg_ = -1;  // the Bool tested last (sc_check): lanes outside it are dead
 public:
     static uint64_t op_valu[256], op_wide[256], op_count[256];
+    int div_ = 0;  // inline division fast paths (op_div): the MH_JIT_DIV level, 0 = off
 private:
 
     // ---- emission
@@ -276,6 +278,11 @@ private:
     void op_vshift(int d, const Val& A, const Val& B, uint8_t op);
     void op_mul(int d, const Val& A, const Val& B);
     void op_div(int d, int a, int b, int cidx, uint32_t kind, int cur);
+    void div_undecided(Opnd decided, int cur);
+    void div_short_dividend(const Val& A, const Val& B, uint32_t kind, int nx, uint32_t dm, int cur,
+                            uint32_t l_cold);
+    void div_small_quotient(const Val& A, const Val& B, uint32_t kind, uint32_t dm, int cur,
+                            uint32_t l_cold);
     void rescue_div_regs(int cur, uint32_t end = R_TEMP0);
     void op_keccak(const SsaInsn& v, int cur);
     void op_exp(int d, const Val& A, const Val& E);
@@ -1321,6 +1328,54 @@ void Emitter::op_div(int d, int a, int b, int cidx, uint32_t kind, int cur) {
     // (every SMT-LIB sign rule reduces to the unsigned form for non-negative x and y)
     if (kind >= 2 && A.l[7].is_c() && !(A.l[7].v >> 31) && B.l[7].is_c() && !(B.l[7].v >> 31))
         kind = kind == 2 ? 0u : 1u;
+    // Inline fast paths (MH_JIT_DIV): what the limbs known to be zero say
+    // about the operands decides most sites without the subroutine.  nx, ny: limbs of x and y
+    // that are not known zero.  The hot side ends in a wave-uniform test over the live lanes; the
+    // cold side is the call as before, and both leave the result in the subroutine's registers.
+    // No pricing emission: the hot sides are at most 3 + 8 (path 1) and 25 (path 3, sdiv 34)
+    // VALU against the 16 or more loads and the ~90 VALU of the call they replace, so every site
+    // that qualifies pays; they allocate no register (v64..v79 and the subroutine's SGPRs are
+    // reserved by any tape that divides).
+    const uint32_t dm = dem_[d];
+    int nx = 8, ny = 8;
+    while (nx > 0 && A.l[nx - 1].is_c(0)) --nx;
+    while (ny > 0 && B.l[ny - 1].is_c(0)) --ny;
+    const uint32_t rbase = kind == 1 ? R_DR : R_DQ;
+    int path = 0;
+    if (div_ >= 1 && ny >= 1 && nx < ny && kind < 4) {
+        if (kind < 2 && B.l[ny - 1].is_c()) {
+            // y >= 2^(32 (ny - 1)) > x at compile time: q = 0, r = x, no code at all
+            Val R;
+            R.defined = true;
+            for (int k = 0; k < 8; ++k) {
+                if (!((dm >> k) & 1)) continue;
+                R.l[k] = kind == 1 && k < nx ? A.l[k] : Limb::C(0);
+                if (R.l[k].is_r()) vretain(R.l[k].v);
+            }
+            vals_[d] = R;
+            return;
+        }
+        path = B.l[ny - 1].is_r() ? 1 : 0;
+        // r = x is copied limb by limb into the result registers: x may sit in them (an earlier
+        // remainder) only limb for limb
+        if (kind & 1)
+            for (int k = 0; k < nx; ++k)
+                if (A.l[k].is_r() && A.l[k].v >= rbase && A.l[k].v < rbase + 8 &&
+                    A.l[k].v != rbase + (uint32_t)k)
+                    path = 0;
+    } else if (div_ >= 3 && nx == 8 && ny == 8 && (kind == 0 || kind == 2)) {
+        path = 3;
+    }
+    uint32_t l_join = 0;
+    if (path) {
+        const uint32_t l_cold = next_lbl_++;
+        l_join = next_lbl_++;
+        if (path == 1) div_short_dividend(A, B, kind, nx, dm, cur, l_cold);
+        else div_small_quotient(A, B, kind, dm, cur, l_cold);
+        emit(M_S_BRANCH, {LBL(l_join)});
+        emit(M_LABEL, {LBL(l_cold)});
+        ++cold_;
+    }
     if (kind < 2) {
         for (int k = 0; k < 8; ++k) emit(M_V_MOV, {V(R_DY + k), src(B.l[k])});
         for (int k = 0; k < 8; ++k) emit(M_V_MOV, {V(R_DR + k), src(A.l[k])});
@@ -1367,10 +1422,137 @@ void Emitter::op_div(int d, int a, int b, int cidx, uint32_t kind, int cur) {
     }
     emit(M_S_MOV_B32, {S(S_DIV_KIND), IMM(kind)});
     emit(M_CALL_DIV, {IMM((uint32_t)code_.size())});
+    if (path) {
+        --cold_;
+        emit(M_LABEL, {LBL(l_join)});
+    }
+    // a remainder of a short dividend is as short on both sides (|r| <= |x|, and x % 0 = x)
+    const int nr = path == 1 && (kind & 1) ? nx : 8;
     Val& R = out(d);
-    const uint32_t dm = dem_[d], base = kind == 1 ? R_DR : R_DQ;
     for (int k = 0; k < 8; ++k)
-        if ((dm >> k) & 1) R.l[k] = Limb::R(base + k);
+        if ((dm >> k) & 1) R.l[k] = k < nr ? Limb::R(rbase + k) : Limb::C(0);
+}
+
+// SCC = some live lane (valid, and true in the Bool tested last) is outside the mask `decided`.
+void Emitter::div_undecided(Opnd decided, int cur) {
+    const Opnd t = S(S_DIV_TM, 2);
+    emit(M_S_ANDN2_B64, {t, S(S_VALID, 2), decided});
+    const int lv = live_vreg_;
+    if (check_ && lv >= 0 && vals_[lv].defined && vals_[lv].is_bool && vals_[lv].bconst < 0 &&
+        last_[lv] > cur)
+        emit(M_S_AND_B64, {t, t, P(vals_[lv].pair)});
+}
+
+// Path 1, a dividend known shorter than the divisor (nx < ny): wherever the divisor's top known
+// limb is nonzero, |x| < |y|, so q = 0 and r = x.  Unsigned kinds test that limb; sdiv / srem
+// arrive here with x >= 0 known and y of unknown sign, and test y7 ^ sign(y), the top limb of
+// ~y for a negative y: nonzero means |y| = ~y + 1 > 2^224 > x.  One live lane with a zero
+// limb sends the wave to the call.
+void Emitter::div_short_dividend(const Val& A, const Val& B, uint32_t kind, int nx, uint32_t dm,
+                                 int cur, uint32_t l_cold) {
+    int ny = 8;
+    while (!B.l[ny - 1].is_r()) --ny;
+    const uint32_t top = B.l[ny - 1].v;
+    if (kind < 2) {
+        emit(M_V_CMP_NE, {VCC(), IMM(0), V(top)});
+    } else {
+        emit(M_V_ASHRREV, {V(R_T1), IMM(31), V(top)});
+        emit(M_V_XOR, {V(R_T1), V(top), V(R_T1)});
+        emit(M_V_CMP_NE, {VCC(), IMM(0), V(R_T1)});
+    }
+    div_undecided(VCC(), cur);
+    emit(M_S_CBRANCH_SCC1, {LBL(l_cold)});
+    const uint32_t base = kind == 1 ? R_DR : R_DQ;
+    for (int k = 0; k < 8; ++k) {
+        if (!((dm >> k) & 1)) continue;
+        if (!(kind & 1)) {
+            emit(M_V_MOV, {V(base + k), IMM(0)});
+        } else if (k < nx && !(A.l[k].is_r() && A.l[k].v == base + (uint32_t)k)) {
+            emit(M_V_MOV, {V(base + k), src(A.l[k])});
+        }
+    }
+}
+
+// Path 3, udiv / sdiv of full-width operands: the subroutine's f32 estimate e of X7:X6 / Y7:Y6
+// (div_routine, L_F32) is the whole quotient wherever it stays clear of an integer.  Error of e
+// against |x| / |y|, relative: each 64-bit window is two conversions and an fma, <= 3 * 2^-24;
+// v_rcp_f32 is 1 ulp, <= 2^-23; the product rounds once, 2^-24 -- together 9 * 2^-24 < 2^-20.8;
+// cutting the operands to their top 64 bits moves each by < 2^-32 (top limb nonzero), and sdiv's
+// windows of x ^ sx, y ^ sy (the one's complement, without the + 1) by at most another 2^-32.
+// With c = trunc(e) the quotient is below c + 1 + 2^-20, so |e - |x|/|y|| < (c + 1) 2^-20.5,
+// and thr = (e + 1) 2^-20 bounds it with a factor 1.4 to spare for its own two roundings.
+// A lane is decided when y's top limb (of y ^ sy) is nonzero, e < 2^10, fract(e) + thr < 1, and
+// fract(e) >= thr -- or e < 1, where the quotient cannot be below 0.  Every live lane decided:
+// q = c (sdiv: negated where the signs differ, the upper limbs are its sign).  Otherwise the call.
+void Emitter::div_small_quotient(const Val& A, const Val& B, uint32_t kind, uint32_t dm, int cur,
+                                 uint32_t l_cold) {
+    const Opnd K32 = S(S_DIV_F64K), KT = S(S_DIV_F64K + 1), ONE = S(S_DIV_YNZ);
+    const Opnd MSK = S(S_DIV_MSK, 2);
+    Opnd x7 = src(A.l[7]), x6 = src(A.l[6]), y7 = src(B.l[7]), y6 = src(B.l[6]);
+    if (kind == 2) {
+        // |v|'s top limbs, up to the + 1: v ^ sign mask (known signs fold)
+        auto tops = [&](const Val& X, uint32_t sreg, uint32_t t, Opnd& h7, Opnd& h6) {
+            if (X.l[7].is_c()) {
+                const uint32_t m = (X.l[7].v >> 31) ? ~0u : 0u;
+                emit(M_V_MOV, {V(sreg), IMM(m)});
+                if (!m) return;
+                h7 = IMM(~X.l[7].v);
+                if (X.l[6].is_c()) h6 = IMM(~X.l[6].v);
+                else { emit(M_V_NOT, {V(t + 1), V(X.l[6].v)}); h6 = V(t + 1); }
+                return;
+            }
+            emit(M_V_ASHRREV, {V(sreg), IMM(31), V(X.l[7].v)});
+            emit(M_V_XOR, {V(t), V(X.l[7].v), V(sreg)});
+            emit(M_V_XOR, {V(t + 1), src(X.l[6]), V(sreg)});
+            h7 = V(t);
+            h6 = V(t + 1);
+        };
+        tops(B, R_SY, R_MAD, y7, y6);
+        tops(A, R_SX, R_CARRY, x7, x6);
+    }
+    emit(M_S_MOV_B32, {K32, IMM(0x4f800000u)});  // 2^32
+    emit(M_V_CVT_F32_U32, {V(R_FT), x7});
+    emit(M_V_CVT_F32_U32, {V(R_FT + 1), x6});
+    emit(M_V_FMA_F32, {V(R_FR), V(R_FT), K32, V(R_FT + 1)});
+    emit(M_V_CVT_F32_U32, {V(R_FT), y7});
+    emit(M_V_CVT_F32_U32, {V(R_FT + 1), y6});
+    emit(M_V_FMA_F32, {V(R_FY), V(R_FT), K32, V(R_FT + 1)});
+    emit(M_V_RCP_F32, {V(R_FY), V(R_FY)});
+    emit(M_S_NOP, {IMM(1)});  // trans result -> non-trans VALU use needs a wait state
+    emit(M_V_MUL_F32, {V(R_FC), V(R_FR), V(R_FY)});
+    emit(M_V_CMP_GT_F32, {VCC(), IMM(0x44800000u), V(R_FC)});  // e < 2^10 (false for NaN, inf)
+    emit(M_S_MOV_B64, {MSK, VCC()});
+    if (y7.k == O_V) {
+        emit(M_V_CMP_NE, {VCC(), IMM(0), y7});
+        emit(M_S_AND_B64, {MSK, MSK, VCC()});
+    } else if (y7.v == 0) {
+        emit(M_S_MOV_B64, {MSK, IMM(0)});
+    }
+    emit(M_V_FRACT_F32, {V(R_FT), V(R_FC)});
+    emit(M_S_MOV_B32, {KT, IMM(0x35800000u)});  // 2^-20
+    emit(M_V_FMA_F32, {V(R_T1), V(R_FC), KT, KT});  // thr
+    emit(M_V_CMP_GT_F32, {VCC(), V(R_T1), V(R_FT)});  // the fraction below thr ...
+    emit(M_S_MOV_B64, {S(S_DIV_TM, 2), VCC()});
+    emit(M_V_CMP_LE_F32, {VCC(), IMM(0x3f800000u), V(R_FC)});  // ... of an estimate >= 1
+    emit(M_S_AND_B64, {S(S_DIV_TM, 2), S(S_DIV_TM, 2), VCC()});
+    emit(M_S_ANDN2_B64, {MSK, MSK, S(S_DIV_TM, 2)});
+    emit(M_S_MOV_B32, {ONE, IMM(0x3f800000u)});
+    emit(M_V_FMA_F32, {V(R_T1), V(R_T1), ONE, V(R_FT)});  // fraction + thr
+    emit(M_V_CMP_LE_F32, {VCC(), IMM(0x3f800000u), V(R_T1)});  // >= 1
+    emit(M_S_ANDN2_B64, {MSK, MSK, VCC()});
+    div_undecided(MSK, cur);
+    emit(M_S_CBRANCH_SCC1, {LBL(l_cold)});
+    emit(M_V_CVT_U32_F32, {V(R_DQ), V(R_FC)});
+    if (kind == 2) {
+        emit(M_V_XOR, {V(R_T1), V(R_SX), V(R_SY)});
+        emit(M_V_XOR, {V(R_DQ), V(R_DQ), V(R_T1)});
+        emit(M_V_SUB_U32, {V(R_DQ), V(R_DQ), V(R_T1)});
+    }
+    for (int k = 1; k < 8; ++k) {
+        if (!((dm >> k) & 1)) continue;
+        if (kind == 2) emit(M_V_ASHRREV, {V(R_DQ + k), IMM(31), V(R_DQ)});
+        else emit(M_V_MOV, {V(R_DQ + k), IMM(0)});
+    }
 }
 
 // KECCAK (exec.h keccak_words): the caller absorbs the message words straight into the
@@ -2041,7 +2223,10 @@ void Emitter::emit_staged(const Stage& sg) {
     if (decided) emit(M_LABEL, {LBL(l_join)});
     vals_[c.d] = bool_mask(q);
     if (!decided || hot + kStageMargin > full) stage_rejected_.push_back(c.d);
-    if (check_ && (*check_)[c.d]) sc_check(vals_[c.d]);
+    if (check_ && (*check_)[c.d]) {
+        sc_check(vals_[c.d]);
+        live_vreg_ = c.d;
+    }
 }
 
 // One SSA instruction.  slice: emitted under a slice demand into temporaries (emit_staged) --
@@ -2147,7 +2332,10 @@ void Emitter::emit_insn(int i, bool slice, bool no_check) {
         seen[ns++] = r;
         release(vals_[r]);
     }
-    if (check_ && !slice && !no_check && (*check_)[v.d]) sc_check(vals_[v.d]);
+    if (check_ && !slice && !no_check && (*check_)[v.d]) {
+        sc_check(vals_[v.d]);
+        live_vreg_ = v.d;
+    }
     if (insn_cost_ && !slice) {
         // a division-family call runs ~90 VALU in the subroutine (tests/tools/jit_mix.py)
         const bool call = op >= D_UDIV_R && op <= D_SMOD_C;
@@ -3750,6 +3938,16 @@ static int stage_level() {
     return e ? std::min(3, std::max(0, atoi(e))) : 3;
 }
 
+// Inline division fast paths (Emitter::op_div): MH_JIT_DIV = 0 off, 1 dividends known shorter
+// than the divisor, 2 the same (reserved for the short-divisor long division), 3 + small quotients
+// of full-width operands.  MH_JIT_STAGE=0 asks for the plain code and switches them off as well.
+static int div_level() {
+    const char* s = std::getenv("MH_JIT_STAGE");  // read per tape, like stage_level()
+    if (s && atoi(s) <= 0) return 0;
+    const char* e = std::getenv("MH_JIT_DIV");
+    return e ? std::min(3, std::max(0, atoi(e))) : 3;
+}
+
 uint64_t sc_fallbacks(bool reset) {
     return reset ? g_sc_fallbacks.exchange(0) : g_sc_fallbacks.load();
 }
@@ -3767,9 +3965,13 @@ TapeCode emit_tape(const SsaTape& st, const std::vector<uint32_t>& pool, uint32_
 TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, uint32_t n_vars,
                         const Options& opt) {
     // source order first: the tape's code when there is no conjunction to reorder, and the VALU
-    // each SSA instruction costs (the scheduler's cost model) when there is
+    // each SSA instruction costs (the scheduler's cost model) when there is.  The prices are
+    // those of the called division (the pricing emission keeps the plain sites), so the inline
+    // paths leave the conjunct order as it was.
+    const int dlevel = div_level();
     std::vector<double> cost;
     Emitter e(st, pool, n_vars, opt, nullptr, opt.short_circuit ? &cost : nullptr);
+    e.div_ = opt.short_circuit ? 0 : dlevel;
     TapeCode tc0 = e.run();
     if (opt.short_circuit) {
         SsaTape sc;
@@ -3781,21 +3983,30 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
                 // against its full cone), a second keeps those that pay
                 Emitter e2(sc, pool, n_vars, opt, &check);
                 e2.stage_ = level;
+                e2.div_ = dlevel;
                 TapeCode tc = e2.run();
                 if (tc.ok && !e2.stage_rejected_.empty()) {
                     std::vector<uint8_t> skip((size_t)sc.n_vregs, 0);
                     for (int d : e2.stage_rejected_) skip[(size_t)d] = 1;
                     Emitter e3(sc, pool, n_vars, opt, &check);
                     e3.stage_ = level;
+                    e3.div_ = dlevel;
                     e3.stage_skip_ = &skip;
                     tc = e3.run();
                 }
                 if (tc.ok) return tc;  // else (register pressure of the slices): unstaged
             }
             Emitter e2(sc, pool, n_vars, opt, &check);
+            e2.div_ = dlevel;
             TapeCode tc = e2.run();
             if (tc.ok) return tc;  // else (register pressure of the new order): source order
             g_sc_fallbacks.fetch_add(1, std::memory_order_relaxed);
+        }
+        if (dlevel > 0 && tc0.ok && tc0.calls_div) {  // source order, with the inline sites
+            Emitter e4(st, pool, n_vars, opt);
+            e4.div_ = dlevel;
+            TapeCode tc = e4.run();
+            if (tc.ok) return tc;
         }
     }
     return tc0;

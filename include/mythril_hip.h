@@ -70,9 +70,15 @@ enum mh_op {
     MH_OP_EVM_SIGNEXTEND = 71,/* a = byte index k, b = x (yellow-paper SIGNEXTEND)                 */
     MH_OP_EVM_BYTE = 72,      /* a = byte index i, b = x (yellow-paper BYTE)                       */
     MH_OP_EVM_ADDMOD = 73,    /* (a + b) mod c, exact sum (yellow-paper ADDMOD); c == 0 gives 0, or */
-    MH_OP_EVM_MULMOD = 74     /* (a * b) mod c ...  with imm0 = 1 the low 256 bits of a op b: the
+    MH_OP_EVM_MULMOD = 74,    /* (a * b) mod c ...  with imm0 = 1 the low 256 bits of a op b: the
                                  value of z3's extract[255:0](bvurem(zext a op zext b, zext c)),
                                  a shape mh_tapes_compile also recognises and rewrites to these */
+    /* (80..84 are host-only term kinds of the Python term layer, never sent here) */
+    MH_OP_LOOKUP = 85         /* table imm0 (of the mh_tables a values call is given) at the key a,
+                                 1..768 bits; imm1 = 0: its value there, else the table's else
+                                 value (width = the table's range, 1..256); imm1 = 1: the Bool
+                                 "the key is in the table".  Tapes holding it only run through
+                                 mh_eval_values_tables                                          */
 };
 
 typedef struct mh_node {
@@ -427,6 +433,33 @@ int32_t mh_eval_values_many(mh_ctx* ctx, const mh_tapeset* ts, const uint32_t* t
                             const mh_assign* as, uint64_t row, uint32_t* out /* [8*n] */);
 /* Kernel launches mh_eval_values_many has made on this context (a test / latency counter).     */
 int32_t mh_ctx_eval_launches(const mh_ctx* ctx, uint64_t* launches);
+
+/* ---- table sets (MH_OP_LOOKUP; DESIGN.md §5.2 "table lookup") ---------------------------------
+ * A set of n_tables finite maps, resident on the device: table t has counts[t] entries whose
+ * keys are nws[t] (1..3) 256-bit words wide.  Its keys start at limb key_offsets[t] of `keys`,
+ * 8 * nws[t] u32 limbs per entry, least significant limb first, STRICTLY ASCENDING as unsigned
+ * integers; its values at limb value_offsets[t] of `values`, 8 limbs per entry; its else value
+ * (what a key outside the table reads) is else_values[8 t ..].  An empty table is legal.
+ * Unsorted or repeated keys, nws outside 1..3 and a table reaching past n_key_limbs /
+ * n_value_limbs are MH_E_INVALID: the kernel trusts what this call checked.                     */
+typedef struct mh_tables mh_tables;
+int32_t mh_tables_create(mh_ctx* ctx, uint32_t n_tables, const uint32_t* counts,
+                         const uint32_t* nws, const uint64_t* key_offsets, const uint32_t* keys,
+                         uint64_t n_key_limbs, const uint64_t* value_offsets,
+                         const uint32_t* values, uint64_t n_value_limbs,
+                         const uint32_t* else_values, mh_tables** out);
+int32_t mh_tables_destroy(mh_tables* tables);
+/* mh_eval_values_many over tapes that may hold MH_OP_LOOKUP, for rows [row_first, row_first +
+ * row_count) of `as`: out[(i * 8 + k) * row_count + r] = limb k of tapes[i]'s root at row r.  One
+ * launch per register class among the listed tapes.  A tape set whose lookups name a table id
+ * `tables` lacks, or a key of another word count than the table's, is MH_E_INVALID.  Every other
+ * entry point that runs tapes (mh_run*, mh_query_round, mh_eval_values*, mh_tapes_jit,
+ * mh_jit_eval_all, mh_repair_score) refuses a tape set holding a lookup with MH_E_UNSUPPORTED
+ * before it launches anything: they have no tables.                                             */
+int32_t mh_eval_values_tables(mh_ctx* ctx, const mh_tapeset* ts, const mh_tables* tables,
+                              const uint32_t* tapes, uint32_t n, const mh_assign* as,
+                              uint64_t row_first, uint64_t row_count,
+                              uint32_t* out /* [n][8][row_count] */);
 
 /* ---- repair of near-miss rows (no reference counterpart; DESIGN.md §6 "repair") ----------------
  * A query's harvested sets override each other: a row satisfies one conjunct's inversion and

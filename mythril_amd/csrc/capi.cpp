@@ -261,6 +261,16 @@ struct mh_tapeset {
     uint32_t bucket_off_unsplit[mh::kNumVariants + 1] = {};
     uint32_t bucket_off_parts[mh::kNumVariants + 1] = {};
     uint32_t *d_ids_unsplit = nullptr, *d_part_ids = nullptr, *d_split = nullptr;
+    // table lookups (MH_OP_LOOKUP): a tape that runs one (F_TABLE) makes the set runnable by
+    // mh_eval_values_tables only; the (table id, key words) pairs the tapes' nodes name
+    bool has_tables = false;
+    std::vector<std::pair<uint32_t, uint32_t>> lookups;
+};
+
+struct mh_tables {
+    mh_ctx* ctx = nullptr;
+    uint32_t* d = nullptr;          // the packed set (dev_isa.h layout)
+    std::vector<uint32_t> nws;      // key words per table
 };
 
 struct mh_assign {
@@ -352,6 +362,15 @@ int32_t check_run_args(const mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_fi
     return MH_OK;
 }
 
+// Every entry point but mh_eval_values_tables: it has no table set for a lookup to read.
+int32_t refuse_tables(const mh_tapeset* ts) {
+    if (ts && ts->has_tables)
+        return set_err(MH_E_UNSUPPORTED,
+                       "the tape set holds table lookups (MH_OP_LOOKUP): only "
+                       "mh_eval_values_tables runs it");
+    return MH_OK;
+}
+
 mh::KParams make_params(const mh_tapeset* ts, uint32_t tape_first, const mh_assign* as,
                         uint64_t row_first, uint64_t row_count, uint64_t index_base,
                         uint32_t mode) {
@@ -417,6 +436,10 @@ int32_t launch_jit(mh_ctx* ctx, const mh_tapeset* ts, const mh_assign* as, uint6
 }
 
 }  // namespace
+
+static int32_t eval_values_rows(mh_ctx* ctx, const mh_tapeset* ts, const mh_tables* tables,
+                                const uint32_t* tapes, uint32_t n, const mh_assign* as,
+                                uint64_t row, uint64_t row_count, uint32_t* out, const char* who);
 
 extern "C" {
 
@@ -739,6 +762,7 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
         std::vector<mh_dev_tape> pheads;
         for (uint32_t t = 0; split_min && t < n_tapes; ++t) {
             if (info[t].n_insns < split_min || !heads[t].root_bool) continue;
+            if (info[t].features & F_TABLE) continue;  // never run by mh_run_async
             const uint64_t b = tape_offsets[t], e = tape_offsets[t + 1];
             const uint32_t want = std::min<uint32_t>(kMaxParts, (info[t].n_insns + split_min - 1) / split_min);
             std::vector<std::vector<mh_node>> parts;
@@ -833,6 +857,10 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
         ts->bucket_off_parts[v] = off_parts[v];
     }
     ts->info = std::move(info);
+    for (const mh_tape_info& ti : ts->info) ts->has_tables |= (ti.features & F_TABLE) != 0;
+    for (uint32_t t = 0; t < n_tapes; ++t)
+        mh::tape_lookups(nodes + tape_offsets[t], (size_t)(tape_offsets[t + 1] - tape_offsets[t]),
+                         ts->lookups);
     ts->n_parts = (uint32_t)part_parent.size();
     ts->ids_unsplit = std::move(ids_unsplit);
     ts->part_ids = std::move(part_ids);
@@ -973,6 +1001,55 @@ int32_t mh_assign_destroy(mh_assign* as) {
     if (as->d_guide) (void)hipFree(as->d_guide);
     mh_ctx* ctx = as->ctx;
     delete as;
+    ctx_unref(ctx);
+    return MH_OK;
+}
+
+int32_t mh_tables_create(mh_ctx* ctx, uint32_t n_tables, const uint32_t* counts,
+                         const uint32_t* nws, const uint64_t* key_offsets, const uint32_t* keys,
+                         uint64_t n_key_limbs, const uint64_t* value_offsets,
+                         const uint32_t* values, uint64_t n_value_limbs,
+                         const uint32_t* else_values, mh_tables** out) {
+    if (!ctx || !out) return set_err(MH_E_INVALID, "null argument");
+    *out = nullptr;
+    std::vector<uint32_t> packed;
+    std::string err;
+    try {
+        if (int32_t r = mh::pack_tables(n_tables, counts, nws, key_offsets, keys, n_key_limbs,
+                                        value_offsets, values, n_value_limbs, else_values, packed,
+                                        err))
+            return set_err(r, "mh_tables_create: " + err);
+    } catch (const std::bad_alloc&) {
+        return set_err(MH_E_NOMEM, "host allocation of the table set");
+    }
+    if (int32_t r = use_device(ctx)) return r;
+    mh_tables* tb = new (std::nothrow) mh_tables();
+    if (!tb) return set_err(MH_E_NOMEM, "table set allocation");
+    tb->ctx = ctx;
+    ++ctx->children;
+    tb->nws.assign(nws, nws + n_tables);
+    // a pool block like a tape set's: a certified hit allocates nothing after the first
+    hipError_t e = pool_alloc(ctx, &tb->d, packed.size() * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(tb->d, packed.data(), packed.size() * sizeof(uint32_t),
+                           hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // `packed` is pageable and local
+    if (e != hipSuccess) {
+        mh_tables_destroy(tb);
+        return set_err(MH_E_DEVICE, std::string("table set upload: ") + hipGetErrorString(e));
+    }
+    *out = tb;
+    return MH_OK;
+}
+
+int32_t mh_tables_destroy(mh_tables* tb) {
+    if (!tb) return MH_OK;
+    settle(tb->ctx);
+    (void)hipSetDevice(tb->ctx->device);
+    if (tb->ctx->stream) (void)hipStreamSynchronize(tb->ctx->stream);
+    pool_free(tb->ctx, tb->d);
+    mh_ctx* ctx = tb->ctx;
+    delete tb;
     ctx_unref(ctx);
     return MH_OK;
 }
@@ -1172,6 +1249,7 @@ int32_t mh_run_async(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first, uin
                      uint64_t* d_hit_count) {
     if (int32_t r = check_run_args(ctx, ts, tape_first, tape_count, as, row_first, row_count, mode))
         return r;
+    if (int32_t r = refuse_tables(ts)) return r;
     if (int32_t r = use_device(ctx)) return r;
     mh::KParams p = make_params(ts, tape_first, as, row_first, row_count, index_base, mode);
     p.first_hit = reinterpret_cast<unsigned long long*>(d_first_hit);
@@ -1321,6 +1399,7 @@ int32_t mh_run_rows(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first, uint
         return r;
     if (n_cols && (!rows_out || n_cols > as->n_vars))
         return set_err(MH_E_INVALID, "mh_run_rows: rows_out null or n_cols beyond the buffer's columns");
+    if (int32_t r = refuse_tables(ts)) return r;
     if (int32_t r = use_device(ctx)) return r;
     const size_t n = std::max<uint32_t>(tape_count, 1);
     const size_t res_bytes = 2 * n * sizeof(uint64_t);
@@ -1365,6 +1444,7 @@ int32_t mh_query_round(mh_ctx* ctx, const mh_tapeset* ts, mh_assign* as, const m
                        uint64_t* hit_count, uint32_t n_cols, uint32_t* rows_out) {
     if (!ctx || !as || as->ctx != ctx) return set_err(MH_E_INVALID, "null or foreign assignment buffer");
     if (int32_t r = check_run_args(ctx, ts, tape_first, tape_count, as, 0, count, mode)) return r;
+    if (int32_t r = refuse_tables(ts)) return r;
     // the generator, the run and the copy queue back to back on the ctx stream: one host sync
     if (int32_t r = mh_assign_generate_guided(as, seed, global_base, 0, count, guide)) return r;
     return mh_run_rows(ctx, ts, tape_first, tape_count, as, 0, count, global_base, mode, first_hit,
@@ -1376,6 +1456,7 @@ int32_t mh_eval_values(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape, const m
     if (int32_t r = check_run_args(ctx, ts, tape, 1, as, row_first, row_count, MH_MODE_COUNT_ALL))
         return r;
     if (!out && row_count) return set_err(MH_E_INVALID, "null out");
+    if (int32_t r = refuse_tables(ts)) return r;
     if (row_count == 0) return MH_OK;
     if (int32_t r = use_device(ctx)) return r;
     const uint32_t variant = mh::variant_of(ts->info[tape].n_regs, ts->info[tape].features);
@@ -1408,9 +1489,45 @@ int32_t mh_eval_values(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape, const m
 
 int32_t mh_eval_values_many(mh_ctx* ctx, const mh_tapeset* ts, const uint32_t* tapes,
                             uint32_t n, const mh_assign* as, uint64_t row, uint32_t* out) {
-    if (int32_t r = check_run_args(ctx, ts, 0, 0, as, row, 1, MH_MODE_COUNT_ALL)) return r;
-    if (n == 0) return MH_OK;
+    return eval_values_rows(ctx, ts, nullptr, tapes, n, as, row, 1, out, "mh_eval_values_many");
+}
+
+int32_t mh_eval_values_tables(mh_ctx* ctx, const mh_tapeset* ts, const mh_tables* tables,
+                              const uint32_t* tapes, uint32_t n, const mh_assign* as,
+                              uint64_t row_first, uint64_t row_count, uint32_t* out) {
+    if (!tables) return set_err(MH_E_INVALID, "null table set");
+    return eval_values_rows(ctx, ts, tables, tapes, n, as, row_first, row_count, out,
+                            "mh_eval_values_tables");
+}
+
+}  // extern "C"
+
+// mh_eval_values_many (tables == null: one row, tapes with lookups refused) and
+// mh_eval_values_tables: out[(i * 8 + k) * row_count + r]
+static int32_t eval_values_rows(mh_ctx* ctx, const mh_tapeset* ts, const mh_tables* tables,
+                                const uint32_t* tapes, uint32_t n, const mh_assign* as,
+                                uint64_t row, uint64_t row_count, uint32_t* out,
+                                const char* who) {
+    if (int32_t r = check_run_args(ctx, ts, 0, 0, as, row, row_count, MH_MODE_COUNT_ALL)) return r;
+    if (!tables) {
+        if (int32_t r = refuse_tables(ts)) return r;
+    } else {
+        if (tables->ctx != ctx) return set_err(MH_E_INVALID, "table set of another ctx");
+        for (const auto& lk : ts->lookups) {
+            if (lk.first >= tables->nws.size())
+                return set_err(MH_E_INVALID, "a lookup names table " + std::to_string(lk.first) +
+                                                 ", the set has " +
+                                                 std::to_string(tables->nws.size()));
+            if (lk.second != tables->nws[lk.first])
+                return set_err(MH_E_INVALID, "a lookup's key has " + std::to_string(lk.second) +
+                                                 " words, table " + std::to_string(lk.first) +
+                                                 " has " + std::to_string(tables->nws[lk.first]));
+        }
+    }
+    if (n == 0 || row_count == 0) return MH_OK;
     if (!tapes || !out) return set_err(MH_E_INVALID, "null tapes / out");
+    if ((uint64_t)n * 8 * row_count >= (1ull << 31))
+        return set_err(MH_E_INVALID, "values of 2^31 words or more in one call");
     uint32_t top = 0;
     for (uint32_t i = 0; i < n; ++i) {
         if (tapes[i] >= ts->n_tapes) return set_err(MH_E_INVALID, "tape id out of bounds");
@@ -1434,17 +1551,18 @@ int32_t mh_eval_values_many(mh_ctx* ctx, const mh_tapeset* ts, const uint32_t* t
         if (tapes[a.second] != tapes[b.second]) return tapes[a.second] < tapes[b.second];
         return a.second < b.second;
     });
-    // device block: values [n][8], ids [n], first_hit / hit_count [top + 1] each (scratch: the
-    // kernel's count-mode bookkeeping, indexed by tape id)
-    const size_t n_words = (size_t)8 * n + n + 4 * ((size_t)top + 1) + 2;
+    // device block: values [n][8][rows], ids [n], first_hit / hit_count [top + 1] each (scratch:
+    // the kernel's count-mode bookkeeping, indexed by tape id)
+    const size_t nv = (size_t)8 * n * row_count;  // value words
+    const size_t n_words = nv + n + 4 * ((size_t)top + 1) + 2 + (nv & 1);
     std::vector<uint32_t> h(n + 4 * ((size_t)top + 1) + 2, 0u);
     for (uint32_t i = 0; i < n; ++i) h[i] = tapes[by_var[i].second];
     // the ctx's grow-only result buffer (stream-ordered after any earlier use of it)
     void* dv = nullptr;
     MH_HIP(ctx_dbuf(ctx, n_words * sizeof(uint32_t), &dv));
     uint32_t* d = static_cast<uint32_t*>(dv);
-    uint32_t* d_ids = d + 8 * (size_t)n;
-    uint32_t* d_res = d_ids + n + ((n & 1) ? 1 : 0);  // 8-byte aligned
+    uint32_t* d_ids = d + nv;
+    uint32_t* d_res = d_ids + n + (((nv + n) & 1) ? 1 : 0);  // 8-byte aligned
     hipError_t e = hipMemcpyAsync(d_ids, h.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice,
                                   ctx->stream);
     if (e == hipSuccess)
@@ -1456,29 +1574,32 @@ int32_t mh_eval_values_many(mh_ctx* ctx, const mh_tapeset* ts, const uint32_t* t
     for (uint32_t i = 0; i < n && e == hipSuccess;) {
         uint32_t j = i;
         while (j < n && by_var[j].first == by_var[i].first) ++j;
-        mh::KParams p = make_params(ts, 0, as, row, 1, 0, MH_MODE_COUNT_ALL);
+        mh::KParams p = make_params(ts, 0, as, row, row_count, 0, MH_MODE_COUNT_ALL);
+        p.tables = tables ? tables->d : nullptr;
         p.tape_ids = d_ids + i;
         p.n_ids = j - i;
         p.first_hit = reinterpret_cast<unsigned long long*>(d_res);
         p.hit_count = reinterpret_cast<unsigned long long*>(d_res + 2 * ((size_t)top + 1));
-        p.values_out = d + 8 * (size_t)i;
+        p.values_out = d + 8 * (size_t)i * row_count;
         e = mh::launch_sieve(p, by_var[i].first, ctx->stream);
         ++launches;
         i = j;
     }
-    std::vector<uint32_t> vals((size_t)8 * n);
+    std::vector<uint32_t> vals(nv);
     if (e == hipSuccess)
         e = hipMemcpyAsync(vals.data(), d, vals.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
                            ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess)
-        return set_err(MH_E_DEVICE, std::string("mh_eval_values_many: ") + hipGetErrorString(e));
+        return set_err(MH_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     for (uint32_t i = 0; i < n; ++i)
-        std::memcpy(out + 8 * (size_t)by_var[i].second, vals.data() + 8 * (size_t)i,
-                    8 * sizeof(uint32_t));
+        std::memcpy(out + 8 * (size_t)by_var[i].second * row_count,
+                    vals.data() + 8 * (size_t)i * row_count, 8 * row_count * sizeof(uint32_t));
     ctx->eval_launches += launches;
     return MH_OK;
 }
+
+extern "C" {
 
 int32_t mh_ctx_eval_launches(const mh_ctx* ctx, uint64_t* launches) {
     if (!ctx || !launches) return set_err(MH_E_INVALID, "null argument");
@@ -1489,6 +1610,7 @@ int32_t mh_ctx_eval_launches(const mh_ctx* ctx, uint64_t* launches) {
 int32_t mh_tapes_jit(mh_tapeset* ts, uint32_t flags, uint32_t max_vgpr) {
     if (!ts) return set_err(MH_E_INVALID, "null tapeset");
     if (ts->has_jit) return set_err(MH_E_INVALID, "tapeset already has native code");
+    if (int32_t r = refuse_tables(ts)) return r;
     if (int32_t r = use_device(ts->ctx)) return r;
     const auto t0 = std::chrono::steady_clock::now();
     mh::jit::Options opt;
@@ -1649,6 +1771,7 @@ int32_t mh_jit_eval_all(mh_ctx* ctx, const mh_tapeset* ts, const mh_assign* as,
     if (int32_t r = check_run_args(ctx, ts, 0, ts ? ts->n_tapes : 0, as, row_first, row_count,
                                    MH_MODE_COUNT_ALL))
         return r;
+    if (int32_t r = refuse_tables(ts)) return r;
     if (!ts->has_jit) return set_err(MH_E_INVALID, "no native code (mh_tapes_jit first)");
     for (const auto& j : ts->jit)
         if (j.n_groups && !j.vfn) return set_err(MH_E_INVALID, "built without MH_JIT_VALUES");
@@ -1875,6 +1998,7 @@ int32_t mh_repair_score(mh_repair* r, const mh_tapeset* ts, uint32_t tape_first,
     if (int32_t rc = check_run_args(ctx, ts, tape_first, tape_count, as, row_first, row_count,
                                     MH_MODE_COUNT_ALL))
         return rc;
+    if (int32_t rc = refuse_tables(ts)) return rc;
     if (tape_count < 1 || tape_count > r->max_conj)
         return set_err(MH_E_INVALID, "mh_repair_score: conjunct count outside 1..max_conjuncts");
     if (row_count < 1 || row_count > r->max_rows || row_first + row_count > (1ull << 32))

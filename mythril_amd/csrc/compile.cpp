@@ -523,7 +523,7 @@ int arity(const mh_node& nd) {
     if (nd.op == MH_OP_ITE || nd.op == MH_OP_EVM_ADDMOD || nd.op == MH_OP_EVM_MULMOD) return 3;
     if (nd.op == MH_OP_BVNEG || nd.op == MH_OP_BVNOT || nd.op == MH_OP_NOT ||
         nd.op == MH_OP_EXTRACT || nd.op == MH_OP_ZEXT || nd.op == MH_OP_SEXT ||
-        nd.op == MH_OP_KECCAK)
+        nd.op == MH_OP_KECCAK || nd.op == MH_OP_LOOKUP)
         return 1;
     return 2;
 }
@@ -919,6 +919,40 @@ bool Lowering::lower(std::vector<Val>& vals) {
                 out.vreg = v.d;
                 break;
             }
+            case MH_OP_LOOKUP: {
+                // a = key (1..768 bits), imm0 = table id, imm1 = 1: the Bool "key present"
+                const uint32_t wa = W(nd.a);
+                if (wa == 0 || wa > 768) return fail("lookup key outside 1..768 bits");
+                if (nd.imm0 > MH_AUX_MAX) return fail("table id exceeds 14 bits");
+                if (nd.imm1 > 1 || (nd.imm1 ? w != 0 : (w == 0 || w > 256)))
+                    return fail("bad lookup form / range width");
+                features |= F_TABLE;
+                // re-cut the key (pieces, most significant first) into little-endian 256-bit
+                // words, low word first, the way the keccak message is cut into its words
+                const auto ps = pieces_of(nd.a, wa);
+                const uint32_t nw = (wa + 255) / 256;
+                int words[3] = {-1, -1, -1};
+                uint32_t o = wa;  // bit offset (from the key's low end) of the piece's top
+                for (const Piece& p : ps) {
+                    if (p.bits == 0 || p.bits > 256 || p.bits > o) return fail("bad lookup key piece");
+                    o -= p.bits;
+                    for (uint32_t i = 0; i < nw; ++i) {
+                        if (!(o < 256 * (i + 1) && o + p.bits > 256 * i)) continue;
+                        int part = p.vreg;
+                        if (o > 256 * i) part = shl_imm(part, o - 256 * i);   // mod 2^256
+                        else if (o < 256 * i) part = shr_imm(part, 256 * i - o);
+                        words[i] = words[i] < 0 ? part : emit(D_OR_R, words[i], part, -1);
+                    }
+                }
+                if (o != 0) return fail("bad lookup key pieces");
+                const uint32_t w1 = D_LOOKUP | (nw << 8) | ((nd.imm1 & 1u) << 10) | (nd.imm0 << 17);
+                VInsn v{D_LOOKUP, fresh(), words[0], words[1], words[2], nd.imm1 ? 1u : w, 0, -1,
+                        w1};
+                code.push_back(v);
+                // (a table's values are the caller's: masked, so the value is canonical)
+                out.vreg = nd.imm1 ? v.d : masked(v.d, w);
+                break;
+            }
             default:
                 return fail("unknown op " + std::to_string(nd.op));
         }
@@ -1033,7 +1067,8 @@ int fold_constants(Lowering& L, int root_v, int value_numbering) {
             val[(size_t)v.d * 8] = op == D_TRUE ? 1u : 0u;
             continue;
         }
-        if (op == D_LOADVAR || op == D_KECCAK) continue;
+        // (a lookup's value is the launch's table set's, never the host's to fold)
+        if (op == D_LOADVAR || op == D_KECCAK || op == D_LOOKUP) continue;
         if (op == D_ITE || op == D_BITE) {  // (cond a, then b, else c)
             if (K(v.a)) rep[v.d] = (val[(size_t)v.a * 8] & 1u) ? v.b : v.c;
             continue;
@@ -1098,6 +1133,7 @@ int fold_constants(Lowering& L, int root_v, int value_numbering) {
         const uint8_t op = code[i].op;
         if (op >= D_UDIV_R && op <= D_SMOD_C) feats |= F_DIV;
         else if (op == D_KECCAK) feats |= F_KECCAK;
+        else if (op == D_LOOKUP) feats |= F_TABLE;
         else if (op == D_EXP || op == D_SIGNEXT || op == D_BYTE || op == D_ADDMOD ||
                  op == D_MULMOD)
             feats |= F_EVM;
@@ -1285,6 +1321,7 @@ std::vector<mh_node> rematerialize(const mh_node* t, size_t n, uint32_t max_size
             case MH_OP_BVMUL: case MH_OP_BVUDIV: case MH_OP_BVUREM: case MH_OP_BVSDIV:
             case MH_OP_BVSREM: case MH_OP_BVSMOD: case MH_OP_KECCAK: case MH_OP_EVM_EXP:
             case MH_OP_BVMUL_NOOVFL_U: case MH_OP_EVM_ADDMOD: case MH_OP_EVM_MULMOD:
+            case MH_OP_LOOKUP:
                 ok = false;
                 break;
             default:
@@ -1578,7 +1615,7 @@ int32_t compile_tape_once(const mh_node* nodes, size_t n_nodes, const uint32_t* 
         const uint32_t c = P(v.c);
         uint32_t op = v.op;
         uint32_t w1;
-        if (v.op == D_KECCAK) {
+        if (v.op == D_KECCAK || v.op == D_LOOKUP) {
             w1 = v.w1raw;
         } else {
             if (v.aux > MH_AUX_MAX) {
@@ -1621,11 +1658,84 @@ int32_t compile_tape_once(const mh_node* nodes, size_t n_nodes, const uint32_t* 
 
 }  // namespace
 
+int32_t pack_tables(uint32_t n_tables, const uint32_t* counts, const uint32_t* nws,
+                    const uint64_t* key_offsets, const uint32_t* keys, uint64_t n_key_limbs,
+                    const uint64_t* value_offsets, const uint32_t* values,
+                    uint64_t n_value_limbs, const uint32_t* else_values,
+                    std::vector<uint32_t>& out, std::string& err) {
+    out.clear();
+    if (n_tables > MH_AUX_MAX + 1u) {
+        err = "more tables than a lookup can name";
+        return MH_E_INVALID;
+    }
+    if (n_tables && (!counts || !nws || !key_offsets || !value_offsets || !else_values)) {
+        err = "null table array";
+        return MH_E_INVALID;
+    }
+    uint64_t total = 1 + (uint64_t)MH_TABLE_HEAD * n_tables;
+    for (uint32_t t = 0; t < n_tables; ++t) {
+        const std::string at = "table " + std::to_string(t) + ": ";
+        if (nws[t] < 1 || nws[t] > 3) {
+            err = at + "key words outside 1..3";
+            return MH_E_INVALID;
+        }
+        const uint64_t kl = 8ull * nws[t], n = counts[t];
+        if (key_offsets[t] > n_key_limbs || n * kl > n_key_limbs - key_offsets[t] ||
+            value_offsets[t] > n_value_limbs || n * 8 > n_value_limbs - value_offsets[t]) {
+            err = at + "entries reach past the key / value arrays";
+            return MH_E_INVALID;
+        }
+        if (n && (!keys || !values)) {
+            err = at + "null keys / values";
+            return MH_E_INVALID;
+        }
+        const uint32_t* k = keys + key_offsets[t];
+        for (uint64_t i = 1; i < n; ++i) {  // strictly ascending, most significant limb first
+            int c = 0;
+            for (uint64_t j = kl; j-- > 0 && c == 0;)
+                c = k[(i - 1) * kl + j] < k[i * kl + j] ? -1 : k[(i - 1) * kl + j] > k[i * kl + j];
+            if (c >= 0) {
+                err = at + "keys not strictly ascending at entry " + std::to_string(i);
+                return MH_E_INVALID;
+            }
+        }
+        total += n * (kl + 8);
+    }
+    if (total >= (1ull << 32)) {
+        err = "table set of 2^32 words or more";
+        return MH_E_INVALID;
+    }
+    out.assign((size_t)total, 0u);
+    out[0] = n_tables;
+    uint64_t at = 1 + (uint64_t)MH_TABLE_HEAD * n_tables;
+    for (uint32_t t = 0; t < n_tables; ++t) {
+        uint32_t* h = out.data() + 1 + (size_t)MH_TABLE_HEAD * t;
+        const uint64_t kl = 8ull * nws[t], n = counts[t];
+        h[0] = counts[t];
+        h[1] = nws[t];
+        h[2] = (uint32_t)at;
+        if (n) std::memcpy(out.data() + at, keys + key_offsets[t], (size_t)(n * kl) * 4);
+        at += n * kl;
+        h[3] = (uint32_t)at;
+        if (n) std::memcpy(out.data() + at, values + value_offsets[t], (size_t)(n * 8) * 4);
+        at += n * 8;
+        std::memcpy(h + 4, else_values + 8ull * t, 32);
+    }
+    return MH_OK;
+}
+
+void tape_lookups(const mh_node* nodes, size_t n_nodes,
+                  std::vector<std::pair<uint32_t, uint32_t>>& out) {
+    for (size_t i = 0; i < n_nodes; ++i)
+        if (nodes[i].op == MH_OP_LOOKUP && nodes[i].a < i)
+            out.push_back({nodes[i].imm0, (nodes[nodes[i].a].width + 255u) / 256u});
+}
+
 static int ir_arity(uint8_t op) {
     switch (op) {
         case MH_OP_CONST: case MH_OP_VAR: case MH_OP_TRUE: case MH_OP_FALSE: return 0;
         case MH_OP_BVNEG: case MH_OP_BVNOT: case MH_OP_NOT: case MH_OP_EXTRACT: case MH_OP_ZEXT:
-        case MH_OP_SEXT: case MH_OP_KECCAK: return 1;
+        case MH_OP_SEXT: case MH_OP_KECCAK: case MH_OP_LOOKUP: return 1;
         case MH_OP_ITE: case MH_OP_EVM_ADDMOD: case MH_OP_EVM_MULMOD: return 3;
         default: return 2;
     }

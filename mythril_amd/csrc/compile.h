@@ -92,6 +92,19 @@ int32_t compile_tape(const mh_node* nodes, size_t n_nodes, const uint32_t* const
                      ConstIndex& dconst_index,
                      std::vector<uint32_t>& words, CompiledTape& out, std::string& err);
 
+// mh_tables_create's host half: validates the caller's tables (include/mythril_hip.h: nws in
+// 1..3, keys strictly ascending, every table inside its arrays) and packs them into the device
+// layout of dev_isa.h.  MH_E_INVALID with `err` set when a check fails; nothing is trusted later.
+int32_t pack_tables(uint32_t n_tables, const uint32_t* counts, const uint32_t* nws,
+                    const uint64_t* key_offsets, const uint32_t* keys, uint64_t n_key_limbs,
+                    const uint64_t* value_offsets, const uint32_t* values,
+                    uint64_t n_value_limbs, const uint32_t* else_values,
+                    std::vector<uint32_t>& out, std::string& err);
+
+// The lookups a tape's nodes hold, as (table id, key words) pairs appended to `out`.
+void tape_lookups(const mh_node* nodes, size_t n_nodes,
+                  std::vector<std::pair<uint32_t, uint32_t>>& out);
+
 // A tape whose root is a conjunction, cut into at most `want` parts of consecutive conjuncts of
 // about equal cone size: each part the nodes its conjuncts reach, in tape order and re-indexed,
 // then the AND of its conjuncts, so a row satisfies the tape iff it satisfies every part (the

@@ -20,6 +20,10 @@
 //        F_YC (complex ops only): y is the inline constant rather than R[b]
 //   D_KECCAK: w1 = op | nw << 8 | full << 10: message = nw (1..3) left-aligned 32-byte words
 //             X, R[b], R[c] (big-endian bytes, 0x01 pad already in place unless full = 1)
+//   D_LOOKUP: w1 = op | nw << 8 | hit << 10 | table << 17: the key is nw (1..3) 256-bit words X,
+//             R[b], R[c], little-endian slices of the key (LOW word first, unlike KECCAK's
+//             left-aligned message words); X = the value table `table` holds at that key, else
+//             the table's else value (hit = 1: the Bool "the key is in the table")
 // Ops below D_FIRST_COMPLEX run in the hand-written assembly core (asm_core.inc, threaded
 // code: one computed jump per instruction); the others in C++ (exec.h).  Narrow signed
 // compares, sign extension and arithmetic shifts are lowered by the host onto asm ops
@@ -97,6 +101,8 @@ enum mh_dop : uint8_t {
     D_WINDOW,                      // end of a 64-slot window: continue with the next one
     D_ADDMOD, D_MULMOD,            // EVM ADDMOD / MULMOD: (X op y) mod R[c], exact; aux bit 0:
                                    // R[c] == 0 gives the low 256 bits of X op y (else 0)
+    D_LOOKUP,                      // X = table aux at the key X, R[b], R[c] (below); after D_MULMOD,
+                                   // so D_LOADVAR and the asm core's slots keep their numbers
     D_NUM_OPS
 };
 
@@ -152,7 +158,15 @@ enum { F_YC = 1u << 31 };
 // Feature bits (mh_tape_info.features) — select the kernel variant.  A tape without F_CPLX,
 // F_KECCAK or F_EVM runs entirely in the asm core (a kernel without the C++ path: fewer VGPRs,
 // more waves).  F_DIV is informational (division runs in the asm core).
-enum { F_DIV = 1, F_KECCAK = 2, F_EVM = 4, F_CPLX = 8 /* other C++ ops */ };
+enum { F_DIV = 1, F_KECCAK = 2, F_EVM = 4, F_CPLX = 8 /* other C++ ops */,
+       F_TABLE = 16 /* D_LOOKUP: the tape reads a table set (mh_tables) */ };
+
+// Device layout of a table set (one u32 buffer; the host validates it, mh_tables_create, and
+// the kernel trusts it).  Word 0: the number of tables.  Then one header of MH_TABLE_HEAD words
+// per table: [0] entries, [1] nw (key words of 256 bits), [2] word offset of the keys, [3] word
+// offset of the values, [4..11] the else value; keys 8 * nw limbs each (limb 0 first), strictly
+// ascending as unsigned integers; values 8 limbs each.
+#define MH_TABLE_HEAD 12
 
 // Per-tape header in the device tape table.
 struct mh_dev_tape {

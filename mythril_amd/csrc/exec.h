@@ -10,6 +10,9 @@
 //   void write(u32 r, const u32* v);  R[r] = v
 //   void iconst(u32 slot, u32* v);    the inline constant in slots slot..slot+3 of the tape
 //   void var(u32 col, u32* v);        assignment column col of this lane's row
+//   void lookup(u32 table, u32 nw, const u32* k0, const u32* k1, const u32* k2, u32 hit, u32* z);
+//                                     D_LOOKUP (FEAT & F_TABLE only): table_lookup() below over
+//                                     the machine's table set
 // FEAT (dev_isa.h F_DIV | F_KECCAK | F_EVM) compiles the heavy handlers in or out, so a tape
 // set without them runs a kernel with a smaller register budget (higher occupancy).
 #pragma once
@@ -58,6 +61,51 @@ MH_FN void zero8(u32* z) {
 MH_FN void copy8(u32* z, const u32* x) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) z[k] = x[k];
+}
+
+// D_LOOKUP over a table set T (dev_isa.h layout): binary search of table `table` for the key of
+// nw 256-bit words k0 (low), k1, k2; z = its value, else the table's else value; hit: z = the
+// Bool "found".  Every lane searches its own key (loads through plain pointers: vector loads on
+// the device); an empty table is legal.
+MH_FN int cmp8(const u32* e, const u32* k) {  // -1 / 0 / 1: e < / == / > k, 8 limbs, top first
+    int c = 0;
+#pragma unroll
+    for (int j = 7; j >= 0; --j) {
+        const int cj = e[j] < k[j] ? -1 : e[j] > k[j] ? 1 : 0;
+        c = c != 0 ? c : cj;
+    }
+    return c;
+}
+
+MH_FN void table_lookup(const u32* T, u32 table, u32 nw, const u32* k0, const u32* k1,
+                        const u32* k2, u32 hit, u32* z) {
+    const u32* h = T + 1 + MH_TABLE_HEAD * table;
+    const u32 n = h[0], kl = 8u * nw;
+    const u32* keys = T + h[2];
+    u32 lo = 0, hi = n;  // the first entry >= key
+    bool found = false;
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        const u32* e = keys + mid * kl;  // (the host keeps every offset below 2^32 words)
+        int c = 0;
+        if (nw >= 3u) c = cmp8(e + 16, k2);
+        if (c == 0 && nw >= 2u) c = cmp8(e + 8, k1);
+        if (c == 0) c = cmp8(e, k0);
+        if (c < 0) {
+            lo = mid + 1;
+        } else {
+            hi = mid;
+            found = c == 0;  // hi only moves onto entries >= key: the last one set is entry lo
+        }
+    }
+    zero8(z);
+    if (hit) {
+        z[0] = found ? 1u : 0u;
+        return;
+    }
+    const u32* v = found ? T + h[3] + lo * 8u : h + 4;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) z[k] = v[k];
 }
 
 // z = f(x, y, c3) for a complex op (op >= D_FIRST_COMPLEX): x = R[a'], y = R[b] or the inline
@@ -112,6 +160,11 @@ MH_FN void complex_op(const E& env, u32 w1, const u32* x, const u32* y, const u3
             }
             break;
         case D_LOADVAR: env.var(aux, z); break;
+        case D_LOOKUP:
+            // only a machine with tables has lookup(): the guard keeps every other one compiling
+            if constexpr ((FEAT & F_TABLE) != 0)
+                env.lookup(aux, (w1 >> 8) & 3u, x, y, c3, (w1 >> 10) & 1u, z);
+            break;
         default:
             break;
     }

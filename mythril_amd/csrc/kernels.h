@@ -31,6 +31,7 @@ struct KParams {
     uint32_t mask_base;
     uint32_t pad2;
     uint64_t mask_stride;           // waves of the run's grid (sieve_mask_stride)
+    const uint32_t* tables;         // the table set D_LOOKUP reads (dev_isa.h layout), or null
 };
 
 // Kernel variants: register-file size class (NR 7 / 9 / 15) x feature set (asm only / + C++
@@ -39,18 +40,22 @@ struct KParams {
 inline uint32_t nr_class(uint32_t n_regs) {
     return n_regs <= MH_NR_SMALL ? 0u : n_regs <= MH_NR_MID ? 1u : 2u;
 }
+// Tapes with a table lookup (F_TABLE: the certifier's, never a query round's) get a feature class
+// of their own with every handler, one kernel per register class, numbered after the twelve.
+constexpr uint32_t kFirstTableVariant = 12;
 inline uint32_t variant_of(uint32_t n_regs, uint32_t features) {
+    if (features & F_TABLE) return kFirstTableVariant + nr_class(n_regs);  // 12..14
     const uint32_t fc = (features & F_EVM) ? 3u : (features & F_KECCAK) ? 2u
                         : (features & F_CPLX) ? 1u : 0u;
     return nr_class(n_regs) * 4 + fc;  // 0..11
 }
-constexpr uint32_t kNumVariants = 12;
+constexpr uint32_t kNumVariants = 15;
 // The complex-op variants (feature class != 0) load columns inside the asm core (run_lv) with a
 // 32-bit byte stride per limb plane: their buffers hold fewer than 2^30 rows per column.  The
 // asm-only variants index columns with 64-bit arithmetic and take any capacity.
 constexpr uint64_t kLoadvarMaxCapacity = 1ull << 30;
 inline bool variant_fits(uint32_t variant, uint64_t capacity) {
-    return (variant & 3u) == 0 || capacity < kLoadvarMaxCapacity;
+    return (variant < kFirstTableVariant && (variant & 3u) == 0) || capacity < kLoadvarMaxCapacity;
 }
 
 hipError_t launch_sieve(const KParams& p, uint32_t variant, hipStream_t stream);

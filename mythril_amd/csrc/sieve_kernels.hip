@@ -16,7 +16,8 @@
 // flushed with one atomic per tape per workgroup.
 //
 // Kernel variants (kernels.h variant_of): NR in {7, 9, 15} x {asm only, + C++ overflow
-// predicates / unpinned columns, + keccak, + keccak/EVM};
+// predicates / unpinned columns, + keccak, + keccak/EVM}, and per NR one with every handler and
+// the table lookup (D_LOOKUP; mh_eval_values_tables only);
 // mh_run launches one variant per non-empty bucket of tapes, so a tape set's simple tapes run
 // with the register budget (and occupancy) they need rather than the worst tape's.
 #include <hip/hip_runtime.h>
@@ -111,6 +112,11 @@ struct DevMachine {
     __device__ __forceinline__ void var(u32 col, u32* v) const {
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = p->assign[((u64)col * 8 + k) * p->capacity + lrow];
+    }
+    // D_LOOKUP (the F_TABLE variants only): this lane's key in the launch's table set
+    __device__ __forceinline__ void lookup(u32 table, u32 nw, const u32* k0, const u32* k1,
+                                           const u32* k2, u32 hit, u32* z) const {
+        table_lookup(p->tables, table, nw, k0, k1, k2, hit, z);
     }
 };
 
@@ -726,6 +732,8 @@ hipError_t launch_sieve(const KParams& p, uint32_t variant, hipStream_t stream) 
     // C-ABI refuses such runs first, with MH_E_UNSUPPORTED and a message)
     if (!variant_fits(variant, p.capacity)) return hipErrorInvalidValue;
     constexpr int kCplx = F_CPLX, kKec = F_CPLX | F_KECCAK, kAll = F_CPLX | F_KECCAK | F_EVM;
+    constexpr int kTab = kAll | F_TABLE;
+    if (variant >= kFirstTableVariant && !p.tables) return hipErrorInvalidValue;
     switch (variant) {
         case 0: return launch_variant<MH_NR_SMALL, 0>(p, stream);
         case 1: return launch_variant<MH_NR_SMALL, kCplx>(p, stream);
@@ -738,7 +746,11 @@ hipError_t launch_sieve(const KParams& p, uint32_t variant, hipStream_t stream) 
         case 8: return launch_variant<MH_NR_MAX, 0>(p, stream);
         case 9: return launch_variant<MH_NR_MAX, kCplx>(p, stream);
         case 10: return launch_variant<MH_NR_MAX, kKec>(p, stream);
-        default: return launch_variant<MH_NR_MAX, kAll>(p, stream);
+        case 11: return launch_variant<MH_NR_MAX, kAll>(p, stream);
+        case 12: return launch_variant<MH_NR_SMALL, kTab>(p, stream);
+        case 13: return launch_variant<MH_NR_MID, kTab>(p, stream);
+        case 14: return launch_variant<MH_NR_MAX, kTab>(p, stream);
+        default: return hipErrorInvalidValue;
     }
 }
 

@@ -56,6 +56,9 @@ _config = {
     "fallback_logs": False,  # the fallback writes --solver-log files itself (the reference's)
     "sieve_kwargs": {},
     "enabled": True,
+    "certify": None,    # certify every witness against the original constraints (certify.py)
+                        # before the verifier sees it; None: the SIEVE_CERTIFY environment
+                        # variable ("1" turns it on), off by default
 }
 
 
@@ -67,8 +70,12 @@ class SieveUnavailable(RuntimeError):
 def configure(*, fallback: Optional[Callable] = None, verify: Optional[Callable] = None,
               to_terms: Optional[Callable] = None, enabled: Optional[bool] = None,
               log_writer: Optional[Callable] = None, fallback_logs: Optional[bool] = None,
-              **sieve_kwargs) -> None:
-    """Set the fallback solver, the witness verifier, the term importer and sieve options."""
+              certify: Optional[bool] = None, **sieve_kwargs) -> None:
+    """Set the fallback solver, the witness verifier, the term importer and sieve options.
+    ``certify=True`` (or SIEVE_CERTIFY=1) certifies every witness against the original
+    constraints on the device before it is returned or verified (certify.py)."""
+    if certify is not None:
+        _config["certify"] = bool(certify)
     if fallback is not None:
         _config["fallback"] = fallback
     if log_writer is not None:
@@ -85,6 +92,14 @@ def configure(*, fallback: Optional[Callable] = None, verify: Optional[Callable]
         _config["sieve_kwargs"] = dict(sieve_kwargs)
         close_sieve()
     get_model.cache_clear()
+
+
+def certification_on() -> bool:
+    """configure(certify=...) when set, else SIEVE_CERTIFY=1; off by default."""
+    import os
+
+    c = _config["certify"]
+    return os.environ.get("SIEVE_CERTIFY", "") == "1" if c is None else c
 
 
 def _takes_timeout(fn) -> bool:
@@ -106,7 +121,7 @@ def _verify(verify, constraints, m, left):
 def reset() -> None:
     """Back to defaults (tests, plugin stop)."""
     _config.update(fallback=None, verify=None, to_terms=None, log_writer=None,
-                   fallback_logs=False, sieve_kwargs={}, enabled=True)
+                   fallback_logs=False, sieve_kwargs={}, enabled=True, certify=None)
     close_sieve()
     get_model.cache_clear()
 
@@ -226,6 +241,30 @@ def sieve_model(constraints, timeout_ms: Optional[float] = None):
     conv = _config["to_terms"]  # reads reference terms for Model.eval / Model[decl]
     m = Model(s, ctx, w.schema, w.values, w.index,
               importer=conv if hasattr(conv, "term") else None)
+    if certification_on():
+        # the original constraints under the model's extensional meaning, on the device; a
+        # witness that fails, or one the certifier cannot judge, is handled like a verifier's
+        # rejection, and is dropped from the sieve so it does not seed this query's children
+        from .certify import CertifyUnsupported, certify
+        from .native import Unsupported
+
+        try:
+            verdict = certify(m, terms)
+        except (CertifyUnsupported, Unsupported) as e:
+            stats.sieve_uncertified += 1
+            log.debug("sieve witness not certified: %s", e)
+            verdict = False
+        except Exception as e:  # noqa: BLE001 - a device or ABI error says nothing about the
+            # witness: an error, not a rejection (fail closed: the query goes to the fallback)
+            stats.sieve_errors += 1
+            log.debug("sieve witness certification error: %s", e)
+            return None
+        if not verdict:
+            if verdict is not False:
+                log.debug("sieve witness rejected by certification: %r", verdict)
+            stats.sieve_rejected += 1
+            s.witnesses.pop(key, None)
+            return None
     verify = _config["verify"]
     if verify is not None:
         left = None if timeout_ms is None else timeout_ms - 1000.0 * (time.perf_counter() - t0)

@@ -170,27 +170,45 @@ class Model:
         its cells, then its reads -- each at its index term's value under the witness (one
         device batch), where no cell holds that key (lower.py: the read took the cell's branch
         there) -- over the else value (model.py:34-51 reads z3's FuncInterp the same way)."""
+        return self.tables([name])[name]
+
+    def tables(self, names: Optional[Sequence[str]] = None) -> dict:
+        """{name: table(name)} for `names` (default: every array and function symbol the schema
+        has columns or cells of, keccak functions included), the read indices of ALL of them
+        evaluated in one device batch (``table`` costs a batch per symbol)."""
         from .lower import READ_KINDS
 
         sc = self.schema
-        cells = sc.cells.get(name)
-        if cells is None:
-            cells = sc.uf_cells.get(name)
-        cols = [c for c in sc.columns.values() if c.symbol == name]
-        els = [c for c in cols if c.kind in ("else", "ufelse")]
-        reads = sorted((c for c in cols if c.kind in READ_KINDS), key=lambda c: c.key)
-        if cells is None and not els and not reads:
-            return None
-        cells = cells or {}
-        else_v = self.values.get(els[0].name, 0) if els else 0
-        tab = {k: self.values.get(cname, else_v) for k, cname in cells.items()}
-        if reads:
-            at = self._evaluate([c.key for c in reads], [], True)
+        if names is None:
+            names = list(dict.fromkeys(
+                [c.symbol for c in sc.columns.values() if c.kind != "var"] +
+                list(sc.cells) + list(sc.uf_cells) + list(sc.keccak)))
+        parts = {}
+        keys: "list[int]" = []
+        for name in names:
+            cells = sc.cells.get(name)
+            if cells is None:
+                cells = sc.uf_cells.get(name)
+            cols = [c for c in sc.columns.values() if c.symbol == name]
+            els = [c for c in cols if c.kind in ("else", "ufelse")]
+            reads = sorted((c for c in cols if c.kind in READ_KINDS), key=lambda c: c.key)
+            parts[name] = (cells, els, reads)
+            keys += [c.key for c in reads]
+        at = self._evaluate(list(dict.fromkeys(keys)), [], True) if keys else {}
+        out = {}
+        for name, (cells, els, reads) in parts.items():
+            if cells is None and not els and not reads:
+                out[name] = None
+                continue
+            cells = cells or {}
+            else_v = self.values.get(els[0].name, 0) if els else 0
+            tab = {k: self.values.get(cname, else_v) for k, cname in cells.items()}
             for c in reads:
                 k = int(at[c.key])
                 if k not in cells:
                     tab.setdefault(k, self.values.get(c.name, 0))
-        return tab, else_v
+            out[name] = (tab, else_v)
+        return out
 
     def _bool_symbol(self, name: str) -> bool:
         """A 1-bit column made by BoolSym (a Bool symbol: z3 gives True / False)."""

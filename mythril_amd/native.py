@@ -83,6 +83,11 @@ SIGNATURES = {
                                          C.POINTER(C.c_double), _u64p]),
     "mh_eval_values_many": (C.c_int32, [_vp, _vp, _u32p, C.c_uint32, _vp, C.c_uint64, _u32p]),
     "mh_ctx_eval_launches": (C.c_int32, [_vp, _u64p]),
+    "mh_tables_create": (C.c_int32, [_vp, C.c_uint32, _u32p, _u32p, _u64p, _u32p, C.c_uint64,
+                                     _u64p, _u32p, C.c_uint64, _u32p, C.POINTER(_vp)]),
+    "mh_tables_destroy": (C.c_int32, [_vp]),
+    "mh_eval_values_tables": (C.c_int32, [_vp, _vp, _vp, _u32p, C.c_uint32, _vp, C.c_uint64,
+                                          C.c_uint64, _u32p]),
     "mh_tapes_jit": (C.c_int32, [_vp, C.c_uint32, C.c_uint32]),
     "mh_tapes_jit_info": (C.c_int32, [_vp, _vp]),
     "mh_tapes_jit_code_id": (C.c_int32, [_vp, _u64p]),
@@ -1125,6 +1130,76 @@ def eval_values_many(ctx: Context, tapes: CompiledTapes, ids: Sequence[int], ass
     _check(ctx.lib.mh_eval_values_many(ctx.h, tapes.h, _ptr(ids_a), len(ids_a), assign.h, row,
                                        _ptr(out)))
     return out[:len(ids_a)]
+
+
+# ---- table sets (include/mythril_hip.h mh_tables_*; Op.LOOKUP) ---------------------------------
+def _key_limbs(v: int, nw: int) -> List[int]:
+    return [(v >> (32 * k)) & 0xFFFFFFFF for k in range(8 * nw)]
+
+
+def pack_tables(tables: Sequence[Tuple[dict, int, int]]):
+    """mh_tables_create's arrays for `tables`, a list of ({key: value}, else value, key bits):
+    (counts, nws, key_offsets, keys, value_offsets, values, else_values), the keys of each table
+    ascending.  Values and the else value are taken mod 2^256, keys mod 2^(256 nw)."""
+    counts, nws, koffs, voffs, keys, vals, elses = [], [], [0], [0], [], [], []
+    for tab, else_v, key_bits in tables:
+        nw = max(1, (key_bits + 255) // 256)
+        mask = (1 << (256 * nw)) - 1
+        norm = {int(k) & mask: int(v) for k, v in tab.items()}
+        counts.append(len(norm))
+        nws.append(nw)
+        for k in sorted(norm):
+            keys.extend(_key_limbs(k, nw))
+            vals.extend(_key_limbs(norm[k] & ((1 << 256) - 1), 1))
+        koffs.append(len(keys))
+        voffs.append(len(vals))
+        elses.extend(_key_limbs(int(else_v) & ((1 << 256) - 1), 1))
+    u32 = lambda x: np.ascontiguousarray(x if len(x) else [0], dtype=np.uint32)  # noqa: E731
+    return (u32(counts), u32(nws), np.ascontiguousarray(koffs[:-1] or [0], dtype=np.uint64),
+            u32(keys), np.ascontiguousarray(voffs[:-1] or [0], dtype=np.uint64), u32(vals),
+            u32(elses), len(keys), len(vals))
+
+
+class Tables:
+    """mh_tables: a set of finite maps on the device, read by Op.LOOKUP tapes."""
+
+    def __init__(self, ctx: "Context", tables: Sequence[Tuple[dict, int, int]]):
+        self.ctx = ctx
+        self.h = None
+        counts, nws, koffs, keys, voffs, vals, elses, n_keys, n_vals = pack_tables(tables)
+        h = C.c_void_p()
+        _check(ctx.lib.mh_tables_create(ctx.h, len(tables), _ptr(counts), _ptr(nws),
+                                        _ptr(koffs, C.c_uint64), _ptr(keys), n_keys,
+                                        _ptr(voffs, C.c_uint64), _ptr(vals), n_vals,
+                                        _ptr(elses), C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            self.ctx.lib.mh_tables_destroy(self.h)
+            self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def tables_create(ctx: "Context", tables: Sequence[Tuple[dict, int, int]]) -> Tables:
+    return Tables(ctx, tables)
+
+
+def eval_values_tables(ctx: "Context", tapes: "CompiledTapes", tables: Tables,
+                       ids: Sequence[int], assign: "Assignments", row_first: int = 0,
+                       row_count: int = 1) -> np.ndarray:
+    """Root values of the tapes `ids`, which may hold Op.LOOKUP over `tables`, at rows
+    [row_first, row_first + row_count) (mh_eval_values_tables): u32 [len(ids), 8, row_count]."""
+    ids_a = np.ascontiguousarray(ids, dtype=np.uint32)
+    out = np.zeros((max(len(ids_a), 1), 8, max(row_count, 1)), dtype=np.uint32)
+    _check(ctx.lib.mh_eval_values_tables(ctx.h, tapes.h, tables.h, _ptr(ids_a), len(ids_a),
+                                         assign.h, row_first, row_count, _ptr(out)))
+    return out[:len(ids_a), :, :row_count]
 
 
 # ---- repair of near-miss rows (include/mythril_hip.h mh_conjuncts_* / mh_repair_*) -------------

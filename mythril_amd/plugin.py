@@ -235,8 +235,8 @@ class SievePlugin(LaserPlugin):
 
         s = SolverStatistics()
         log.info("constraint sieve: %d hits, %d misses, %d unsupported, %d errors, "
-                 "%d rejected", s.sieve_hits, s.sieve_misses, s.sieve_unsupported,
-                 s.sieve_errors, s.sieve_rejected)
+                 "%d rejected (%d of them uncertified)", s.sieve_hits, s.sieve_misses,
+                 s.sieve_unsupported, s.sieve_errors, s.sieve_rejected, s.sieve_uncertified)
         frontend.reset()
 
 

@@ -96,7 +96,7 @@ except Exception:  # z3 / mythril absent: standalone mirrors
     time_handler = _TimeHandler()
 
 _SIEVE_FIELDS = ("sieve_hits", "sieve_misses", "sieve_unsupported", "sieve_errors",
-                 "sieve_rejected")
+                 "sieve_rejected", "sieve_uncertified")
 
 
 class _Stats:

@@ -24,6 +24,7 @@ import numpy as np
 
 BOOL = 0
 MAX_WIDTH = 1088  # 136 bytes: one Keccak block
+MAX_LOOKUP_KEY = 768  # three 256-bit key words (Op.LOOKUP)
 FINISH_CACHE = 256  # tapes of recent AND roots kept per builder (TapeBuilder.finish) ...
 FINISH_CACHE_NODES = 1 << 20  # ... holding at most this many nodes in all (each entry keeps a
                               # node -> index map and the tape: a bound on memory, not entries)
@@ -84,6 +85,10 @@ class Op(enum.IntEnum):
     STORE = 82        # store(a, b = key, c = value)
     SELECT = 83       # select(a = array, b = index) -> range-width bit-vector
     UF = 84           # uninterpreted function application: imm0 = function id, a = argument
+    # a device op again (MH_OP_LOOKUP): table imm0 of the table set the evaluation is given, at
+    # the key a (1..768 bits); imm1 = 0 its value there or the table's else value (width = the
+    # table's range), imm1 = 1 the Bool "the key is in the table".  Built by certify.py only.
+    LOOKUP = 85
 
 
 NODE_DTYPE = np.dtype(
@@ -110,6 +115,7 @@ ARITY = {
     Op.CONST: 0, Op.VAR: 0, Op.TRUE: 0, Op.FALSE: 0,
     Op.BVNEG: 1, Op.BVNOT: 1, Op.NOT: 1, Op.EXTRACT: 1, Op.ZEXT: 1, Op.SEXT: 1, Op.KECCAK: 1,
     Op.ITE: 3, Op.EVM_ADDMOD: 3, Op.EVM_MULMOD: 3, Op.ARRAY: 0, Op.CONST_ARRAY: 1, Op.STORE: 3, Op.UF: 1,
+    Op.LOOKUP: 1,
 }
 for _op in Op:
     ARITY.setdefault(_op, 2)
@@ -278,6 +284,19 @@ class TapeBuilder:
             raise TapeError("%s takes %d bits, got %d" % (name, domain, self.widths[arg]))
         fid = self.symbols.function_id(name, domain, value_range)
         return self._add(Op.UF, value_range, a=arg, imm0=fid)
+
+    def lookup(self, table: int, key: int, value_range: int, hit: bool = False) -> int:
+        """MH_OP_LOOKUP: table `table` at `key` (a bit-vector of 1..768 bits); its value
+        (`value_range` bits, 1..256) or, with `hit`, the Bool "the key is in the table"."""
+        kw = self.widths[key]
+        if kw == BOOL or kw > MAX_LOOKUP_KEY or self.is_array(key):
+            raise TapeError("a lookup key is a bit-vector of 1..%d bits, got %d"
+                            % (MAX_LOOKUP_KEY, kw))
+        # (the id is the builder's; what reaches the device is renumbered below 2^14 per tape set)
+        if not 1 <= value_range <= 256 or not 0 <= table < 1 << 32:
+            raise TapeError("lookup range %d / table id %d" % (value_range, table))
+        return self._add(Op.LOOKUP, BOOL if hit else value_range, a=key, imm0=table,
+                         imm1=1 if hit else 0)
 
     def _array_sort(self, arr: int) -> Tuple[int, int]:
         if not self.is_array(arr):

@@ -410,6 +410,37 @@ int32_t mh_query_round(mh_ctx* ctx, const mh_tapeset* ts, mh_assign* as, const m
                        uint64_t seed, uint64_t global_base, uint64_t count, uint32_t tape_first,
                        uint32_t tape_count, uint32_t mode, uint64_t* first_hit,
                        uint64_t* hit_count, uint32_t n_cols, uint32_t* rows_out);
+/* Many independent guided rounds in one device submission.  A query's first round is 64 one-wave
+ * workgroups on a 256-CU device and costs four to six launches, a copy and a host sync; a batch
+ * runs every job's waves side by side instead: one generator launch per generator form present,
+ * one result reset, one interpreter launch per register class present (with the class's widest
+ * feature set among the jobs' tapes), one witness-row gather, one copy back and one sync.  The
+ * jobs' descriptors, block tables and packed guides go up in one copy.
+ *
+ * Contract: for every job the outputs (first_hit, hit_count, rows_out), and the contents of the
+ * job's mh_assign afterwards, equal what mh_query_round with the same arguments produces (in
+ * MH_MODE_FIRST_HIT hit_count counts the rows the early exit did not skip, as there: only
+ * MH_MODE_COUNT_ALL makes it a function of the arguments).  A batch always walks whole tapes with
+ * the interpreter: the native code of mh_tapes_jit and split-tape parts are not used.
+ *
+ * The whole list is validated before anything is queued or any device call is made, and the
+ * message names the job: a null or foreign handle, two jobs sharing one mh_assign, or n_cols
+ * beyond the buffer's columns is MH_E_INVALID; count above 4096 or above the buffer's capacity,
+ * a tape set holding a lookup, or a kernel variant the buffer's capacity does not fit is
+ * MH_E_UNSUPPORTED.  n_jobs == 0 is MH_OK; more than MH_ROUND_MANY_MAX jobs is MH_E_INVALID
+ * (callers chunk).  With mh_ctx_enable_timing the submission is one span.                        */
+#define MH_ROUND_MANY_MAX 256
+typedef struct mh_round_job {
+    const mh_tapeset* ts;
+    mh_assign* as;
+    const mh_guide* guide;
+    uint64_t seed, global_base, count;          /* count <= 4096 */
+    uint32_t tape_first, tape_count, mode, n_cols;
+    uint64_t* first_hit;                        /* [tape_count] or NULL */
+    uint64_t* hit_count;                        /* [tape_count] or NULL */
+    uint32_t* rows_out;                         /* [tape_count][n_cols][8], NULL when n_cols == 0 */
+} mh_round_job;
+int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jobs);
 /* Device-pointer form: enqueues on the ctx stream and returns.  d_first_hit / d_hit_count are
  * device buffers of tape_count u64; they are NOT reset (callers initialise them to MH_NO_HIT / 0
  * with mh_results_reset), so several launches can accumulate into them.                          */

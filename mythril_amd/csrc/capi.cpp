@@ -87,6 +87,12 @@ struct mh_ctx {
     AsyncCompile* acomp = nullptr;
     // kernel launches of mh_eval_values_many (Model.eval batching is measured by it)
     uint64_t eval_launches = 0;
+    // mh_query_round_many: the jobs' descriptors, block tables and packed guides go up in one
+    // copy from this pinned staging area to this device block (both grow-only; the call ends with
+    // a stream sync, so the next call finds the staging area free)
+    void* h_batch = nullptr;
+    void* d_batch = nullptr;
+    size_t h_batch_bytes = 0, d_batch_bytes = 0;
 };
 
 // One compile at a time, handed to a worker thread that waits on a condition variable (a thread
@@ -551,6 +557,8 @@ void ctx_free(mh_ctx* ctx) {
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->d_buf) (void)hipFree(ctx->d_buf);
     if (ctx->h_buf) (void)hipHostFree(ctx->h_buf);
+    if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
+    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->stage_ev) (void)hipEventDestroy(ctx->stage_ev);
     if (ctx->comm && rccl()) (void)rccl()->comm_destroy(ctx->comm);
@@ -1093,9 +1101,16 @@ int32_t mh_assign_generate(mh_assign* as, uint64_t seed, uint64_t global_base) {
     return MH_OK;
 }
 
-// The guide checked, packed and queued for upload into `as`'s guide buffer (on the ctx stream):
-// *k = its device form.  Shared by the generator and the repair step's mutate (mh_repair_mutate).
-static int32_t stage_guide(mh_assign* as, const mh_guide* g, mh::KGuide* out) {
+// The packed form of a guide: width | pool_off | pool | set_prob | set_off | alt_off | entry_col |
+// entry_val, in words.
+struct GuideLayout {
+    uint32_t nc = 0, ns = 0, n_pool = 0, n_alts = 0, n_ent = 0, n_value_sets = 0;
+    size_t o_width = 0, o_poff = 0, o_pool = 0, o_prob = 0, o_soff = 0, o_aoff = 0, o_ecol = 0,
+           o_eval = 0, words = 0;
+};
+// Every offset and entry of the guide checked on the host (the kernels trust them) and its
+// layout: no device call.
+static int32_t check_guide(const mh_assign* as, const mh_guide* g, GuideLayout* L) {
     if (g->n_cols > as->n_vars) return set_err(MH_E_INVALID, "guide has more columns than the buffer");
     if (g->n_cols && (!g->col_width || !g->pool_off))
         return set_err(MH_E_INVALID, "guide: null column arrays");
@@ -1142,26 +1157,70 @@ static int32_t stage_guide(mh_assign* as, const mh_guide* g, mh::KGuide* out) {
                 return set_err(MH_E_INVALID, "guide: malformed copy entry");
         }
     }
-    if (int32_t r = use_device(as->ctx)) return r;
-    // pack: width | pool_off | pool | set_prob | set_off | alt_off | entry_col | entry_val
-    const size_t o_width = 0, o_poff = o_width + nc, o_pool = o_poff + nc + 1,
-                 o_prob = o_pool + (size_t)n_pool * 8, o_soff = o_prob + ns,
-                 o_aoff = o_soff + ns + 1, o_ecol = o_aoff + n_alts + 1,
-                 o_eval = o_ecol + n_ent, words = o_eval + (size_t)n_ent * 8;
-    std::vector<uint32_t>& h = as->h_guide;
-    h.assign(words, 0);
-    for (uint32_t v = 0; v < nc; ++v) h[o_width + v] = g->col_width[v];
-    if (nc) std::copy(g->pool_off, g->pool_off + nc + 1, h.begin() + o_poff);
-    if (n_pool) std::copy(g->pool, g->pool + (size_t)n_pool * 8, h.begin() + o_pool);
-    for (uint32_t j = 0; j < ns; ++j) h[o_prob + j] = g->set_prob[j];
+    L->nc = nc;
+    L->ns = ns;
+    L->n_pool = n_pool;
+    L->n_alts = n_alts;
+    L->n_ent = n_ent;
+    L->n_value_sets = n_value_sets;
+    L->o_width = 0;
+    L->o_poff = L->o_width + nc;
+    L->o_pool = L->o_poff + nc + 1;
+    L->o_prob = L->o_pool + (size_t)n_pool * 8;
+    L->o_soff = L->o_prob + ns;
+    L->o_aoff = L->o_soff + ns + 1;
+    L->o_ecol = L->o_aoff + n_alts + 1;
+    L->o_eval = L->o_ecol + n_ent;
+    L->words = L->o_eval + (size_t)n_ent * 8;
+    return MH_OK;
+}
+
+// A checked guide packed into h[0, L.words)
+static void pack_guide(const mh_guide* g, const GuideLayout& L, uint32_t* h) {
+    const uint32_t nc = L.nc, ns = L.ns, n_pool = L.n_pool, n_alts = L.n_alts, n_ent = L.n_ent;
+    std::fill(h, h + L.words, 0u);
+    for (uint32_t v = 0; v < nc; ++v) h[L.o_width + v] = g->col_width[v];
+    if (nc) std::copy(g->pool_off, g->pool_off + nc + 1, h + L.o_poff);
+    if (n_pool) std::copy(g->pool, g->pool + (size_t)n_pool * 8, h + L.o_pool);
+    for (uint32_t j = 0; j < ns; ++j) h[L.o_prob + j] = g->set_prob[j];
     if (ns) {
-        std::copy(g->set_off, g->set_off + ns + 1, h.begin() + o_soff);
-        std::copy(g->alt_off, g->alt_off + n_alts + 1, h.begin() + o_aoff);
+        std::copy(g->set_off, g->set_off + ns + 1, h + L.o_soff);
+        std::copy(g->alt_off, g->alt_off + n_alts + 1, h + L.o_aoff);
     }
     if (n_ent) {
-        std::copy(g->entry_col, g->entry_col + n_ent, h.begin() + o_ecol);
-        std::copy(g->entry_val, g->entry_val + (size_t)n_ent * 8, h.begin() + o_eval);
+        std::copy(g->entry_col, g->entry_col + n_ent, h + L.o_ecol);
+        std::copy(g->entry_val, g->entry_val + (size_t)n_ent * 8, h + L.o_eval);
     }
+}
+
+// The device form of a guide packed at `d`
+static mh::KGuide guide_at(const GuideLayout& L, const uint32_t* d) {
+    mh::KGuide k;
+    k.n_cols = L.nc;
+    k.n_sets = L.ns;
+    k.n_value_sets = L.n_value_sets;
+    k.width = d + L.o_width;
+    k.pool_off = d + L.o_poff;
+    k.pool = d + L.o_pool;
+    k.set_prob = d + L.o_prob;
+    k.set_off = d + L.o_soff;
+    k.alt_off = d + L.o_aoff;
+    k.entry_col = d + L.o_ecol;
+    k.entry_val = d + L.o_eval;
+    k.span_words = (uint32_t)(L.o_eval - L.o_prob);
+    return k;
+}
+
+// The guide checked, packed and queued for upload into `as`'s guide buffer (on the ctx stream):
+// *k = its device form.  Shared by the generator and the repair step's mutate (mh_repair_mutate).
+static int32_t stage_guide(mh_assign* as, const mh_guide* g, mh::KGuide* out) {
+    GuideLayout L;
+    if (int32_t r = check_guide(as, g, &L)) return r;
+    if (int32_t r = use_device(as->ctx)) return r;
+    const size_t words = L.words;
+    std::vector<uint32_t>& h = as->h_guide;
+    h.resize(words);
+    pack_guide(g, L, h.data());
     // both buffers grow geometrically: a LASER child's guide is a little larger than its
     // parent's, and a pinned reallocation per query cost ~0.24 ms (hipHostFree 0.19 +
     // hipHostMalloc 0.05, EtherThief-400, profiles/r05o/htrace)
@@ -1193,20 +1252,7 @@ static int32_t stage_guide(mh_assign* as, const mh_guide* g, mh::KGuide* out) {
                           hipMemcpyHostToDevice, as->ctx->stream));
     MH_HIP(hipEventRecord(as->staged, as->ctx->stream));
     as->staged_pending = true;
-    mh::KGuide k;
-    k.n_cols = nc;
-    k.n_sets = ns;
-    k.n_value_sets = n_value_sets;
-    k.width = as->d_guide + o_width;
-    k.pool_off = as->d_guide + o_poff;
-    k.pool = as->d_guide + o_pool;
-    k.set_prob = as->d_guide + o_prob;
-    k.set_off = as->d_guide + o_soff;
-    k.alt_off = as->d_guide + o_aoff;
-    k.entry_col = as->d_guide + o_ecol;
-    k.entry_val = as->d_guide + o_eval;
-    k.span_words = (uint32_t)(o_eval - o_prob);
-    *out = k;
+    *out = guide_at(L, as->d_guide);
     return MH_OK;
 }
 
@@ -1449,6 +1495,211 @@ int32_t mh_query_round(mh_ctx* ctx, const mh_tapeset* ts, mh_assign* as, const m
     if (int32_t r = mh_assign_generate_guided(as, seed, global_base, 0, count, guide)) return r;
     return mh_run_rows(ctx, ts, tape_first, tape_count, as, 0, count, global_base, mode, first_hit,
                        hit_count, n_cols, rows_out);
+}
+
+int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jobs) {
+    // everything below up to use_device() is host-only: a refused batch has queued nothing
+    if (!ctx) return set_err(MH_E_INVALID, "mh_query_round_many: null ctx");
+    if (n_jobs == 0) return MH_OK;
+    if (n_jobs > MH_ROUND_MANY_MAX)
+        return set_err(MH_E_INVALID, "mh_query_round_many: " + std::to_string(n_jobs) +
+                                         " jobs, more than MH_ROUND_MANY_MAX (" +
+                                         std::to_string(MH_ROUND_MANY_MAX) + "): chunk the list");
+    if (!jobs) return set_err(MH_E_INVALID, "mh_query_round_many: null job list");
+    const auto job_err = [](uint32_t i, int32_t code, const std::string& what) {
+        return set_err(code, "mh_query_round_many: job " + std::to_string(i) + ": " + what);
+    };
+    struct JobPlan {
+        GuideLayout L;
+        const uint32_t *lo[mh::batch::kInterpVariants], *hi[mh::batch::kInterpVariants];
+        size_t guide_off = 0, res_off = 0;  // words of the device block / bytes of the results
+    };
+    std::vector<JobPlan> jp(n_jobs);
+    std::vector<mh::batch::JobShape> shapes(n_jobs);
+    size_t res_bytes = 0;
+    uint32_t max_tc = 0;
+    bool any_rows = false;
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        const mh_round_job& j = jobs[i];
+        if (!j.ts || !j.as || !j.guide) return job_err(i, MH_E_INVALID, "null handle");
+        if (j.ts->ctx != ctx || j.as->ctx != ctx)
+            return job_err(i, MH_E_INVALID, "handles of another ctx");
+        for (uint32_t k = 0; k < i; ++k)
+            if (jobs[k].as == j.as)
+                return job_err(i, MH_E_INVALID, "shares its assignment buffer with job " +
+                                                    std::to_string(k));
+        if (j.count > mh::batch::kMaxRows)
+            return job_err(i, MH_E_UNSUPPORTED, std::to_string(j.count) + " rows, more than " +
+                                                    std::to_string(mh::batch::kMaxRows));
+        if (j.count > j.as->capacity)
+            return job_err(i, MH_E_UNSUPPORTED, std::to_string(j.count) +
+                                                    " rows, more than the buffer's capacity");
+        if (int32_t r = check_run_args(ctx, j.ts, j.tape_first, j.tape_count, j.as, 0, j.count,
+                                       j.mode))
+            return job_err(i, r, g_err);
+        if (j.n_cols && (!j.rows_out || j.n_cols > j.as->n_vars))
+            return job_err(i, MH_E_INVALID, "rows_out null or n_cols beyond the buffer's columns");
+        if (int32_t r = refuse_tables(j.ts)) return job_err(i, r, g_err);
+        if (int32_t r = check_guide(j.as, j.guide, &jp[i].L)) return job_err(i, r, g_err);
+        // the job's tapes per interpreter bucket: whole tapes (ts->ids), never split parts
+        mh::batch::JobShape& sh = shapes[i];
+        sh.count = j.count;
+        sh.whole = j.tape_first == 0 && j.tape_count == j.ts->n_tapes;
+        sh.gen_n_cols = jp[i].L.nc;
+        sh.gen_span_words = (uint32_t)(jp[i].L.o_eval - jp[i].L.o_prob);
+        for (uint32_t v = 0; v < mh::batch::kInterpVariants; ++v) {
+            const uint32_t* b = j.ts->ids.data() + j.ts->bucket_off[v];
+            const uint32_t* e = j.ts->ids.data() + j.ts->bucket_off[v + 1];
+            jp[i].lo[v] = std::lower_bound(b, e, j.tape_first);
+            jp[i].hi[v] = std::lower_bound(jp[i].lo[v], e, j.tape_first + j.tape_count);
+            sh.n_ids[v] = (uint32_t)(jp[i].hi[v] - jp[i].lo[v]);
+        }
+        jp[i].res_off = res_bytes;
+        res_bytes += 2 * (size_t)j.tape_count * sizeof(uint64_t) +
+                     (size_t)j.tape_count * j.n_cols * 8 * sizeof(uint32_t);
+        max_tc = std::max(max_tc, j.tape_count);
+        any_rows = any_rows || (j.n_cols && j.tape_count);
+    }
+    // (a job without tapes has no segment, but the generator still writes its rows, as
+    // mh_query_round's does)
+    const mh::batch::Plan plan = mh::batch::plan(shapes.data(), n_jobs);
+    const mh::batch::Plan& gplan = plan;
+    // a launch's variant serves every segment in it: each must fit that segment's buffer
+    for (const auto& l : plan.launches)
+        for (uint32_t b = l.first; b < l.first + l.count; ++b) {
+            const uint32_t job = plan.segments[plan.blocks[b].seg].job;
+            if (!mh::variant_fits(l.variant, jobs[job].as->stride)) {
+                (void)refuse_capacity(jobs[job].as->stride);
+                return job_err(job, MH_E_UNSUPPORTED, g_err);
+            }
+        }
+    // the device block: segments' KParams | GenJob[] | ResultJob[] | block tables | guides
+    const auto align = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_seg = 0;
+    const size_t o_gen = align(o_seg + plan.segments.size() * sizeof(mh::KParams));
+    const size_t o_res = align(o_gen + n_jobs * sizeof(mh::GenJob));
+    const size_t o_blk = align(o_res + n_jobs * sizeof(mh::ResultJob));
+    const size_t o_gblk = align(o_blk + plan.blocks.size() * sizeof(mh::batch::BlockEntry));
+    size_t up_bytes = align(o_gblk + gplan.gen_blocks.size() * sizeof(mh::batch::GenEntry));
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        jp[i].guide_off = up_bytes;
+        up_bytes = align(up_bytes + jp[i].L.words * sizeof(uint32_t));
+    }
+    if (int32_t r = use_device(ctx)) return r;
+    const auto grow = [](size_t have, size_t need) {
+        size_t n = std::max<size_t>(have, 1 << 16);
+        while (n < need) n <<= 1;
+        return n;
+    };
+    if (up_bytes > ctx->h_batch_bytes) {
+        if (ctx->h_batch) MH_HIP(hipHostFree(ctx->h_batch));
+        ctx->h_batch = nullptr;
+        ctx->h_batch_bytes = 0;
+        const size_t n = grow(0, up_bytes);
+        MH_HIP(hipHostMalloc(&ctx->h_batch, n, hipHostMallocDefault));
+        ctx->h_batch_bytes = n;
+    }
+    if (up_bytes > ctx->d_batch_bytes) {
+        if (ctx->d_batch) MH_HIP(hipFree(ctx->d_batch));
+        ctx->d_batch = nullptr;
+        ctx->d_batch_bytes = 0;
+        const size_t n = grow(0, up_bytes);
+        MH_HIP(hipMalloc(&ctx->d_batch, n));
+        ctx->d_batch_bytes = n;
+    }
+    void* dres_v = nullptr;
+    void* hres_v = nullptr;
+    MH_HIP(ctx_dbuf(ctx, std::max<size_t>(res_bytes, 8), &dres_v));
+    MH_HIP(ctx_hbuf(ctx, std::max<size_t>(res_bytes, 8), &hres_v));
+    char* const dres = static_cast<char*>(dres_v);
+    const char* const hres = static_cast<const char*>(hres_v);
+    char* const hb = static_cast<char*>(ctx->h_batch);
+    char* const db = static_cast<char*>(ctx->d_batch);
+    // fill the staging area
+    mh::GenJob* h_gen = reinterpret_cast<mh::GenJob*>(hb + o_gen);
+    mh::ResultJob* h_res = reinterpret_cast<mh::ResultJob*>(hb + o_res);
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        const mh_round_job& j = jobs[i];
+        pack_guide(j.guide, jp[i].L, reinterpret_cast<uint32_t*>(hb + jp[i].guide_off));
+        mh::GenJob g{};
+        g.assign = j.as->d;
+        g.stride = j.as->stride;
+        g.count = j.count;
+        g.seed = j.seed;
+        g.base = j.global_base;
+        g.g = guide_at(jp[i].L, reinterpret_cast<const uint32_t*>(db + jp[i].guide_off));
+        h_gen[i] = g;
+        mh::ResultJob r{};
+        r.first_hit = reinterpret_cast<uint64_t*>(dres + jp[i].res_off);
+        r.assign = j.as->d;
+        r.stride = j.as->stride;
+        r.index_base = j.global_base;
+        r.tc = j.tape_count;
+        r.n_cols = j.n_cols;
+        h_res[i] = r;
+    }
+    mh::KParams* h_seg = reinterpret_cast<mh::KParams*>(hb + o_seg);
+    for (size_t si = 0; si < plan.segments.size(); ++si) {
+        const mh::batch::Segment& sg = plan.segments[si];
+        const mh_round_job& j = jobs[sg.job];
+        mh::KParams p = make_params(j.ts, j.tape_first, j.as, 0, j.count, j.global_base, j.mode);
+        unsigned long long* fh = reinterpret_cast<unsigned long long*>(dres + jp[sg.job].res_off);
+        p.first_hit = fh;
+        p.hit_count = fh + j.tape_count;
+        p.tape_ids = j.ts->d_ids + (jp[sg.job].lo[sg.first_bucket] - j.ts->ids.data());
+        p.n_ids = sg.n_ids;
+        h_seg[si] = p;
+    }
+    if (!plan.blocks.empty())
+        std::memcpy(hb + o_blk, plan.blocks.data(),
+                    plan.blocks.size() * sizeof(mh::batch::BlockEntry));
+    if (!gplan.gen_blocks.empty())
+        std::memcpy(hb + o_gblk, gplan.gen_blocks.data(),
+                    gplan.gen_blocks.size() * sizeof(mh::batch::GenEntry));
+    // one span for the whole submission
+    std::pair<hipEvent_t, hipEvent_t> sp{nullptr, nullptr};
+    if (ctx->timing) {
+        MH_HIP(hipEventCreate(&sp.first));
+        MH_HIP(hipEventCreate(&sp.second));
+        ctx->spans.push_back(sp);
+        MH_HIP(hipEventRecord(sp.first, ctx->stream));
+    }
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, s);
+    const mh::GenJob* d_gen = reinterpret_cast<const mh::GenJob*>(db + o_gen);
+    const mh::ResultJob* d_res = reinterpret_cast<const mh::ResultJob*>(db + o_res);
+    const mh::batch::GenEntry* d_gblk = reinterpret_cast<const mh::batch::GenEntry*>(db + o_gblk);
+    const mh::batch::BlockEntry* d_blk = reinterpret_cast<const mh::batch::BlockEntry*>(db + o_blk);
+    for (const auto& l : gplan.gen_launches)
+        if (e == hipSuccess)
+            e = mh::launch_generate_guided_batch(d_gen, d_gblk + l.first, l.count, l.form,
+                                                 l.lds_bytes, s);
+    if (e == hipSuccess && max_tc) e = mh::launch_results_reset_batch(d_res, n_jobs, s);
+    for (const auto& l : plan.launches)
+        if (e == hipSuccess)
+            e = mh::launch_sieve_batch(reinterpret_cast<const mh::KParams*>(db + o_seg),
+                                       d_blk + l.first, l.count, l.variant, s);
+    if (e == hipSuccess && any_rows) e = mh::launch_witness_rows_batch(d_res, n_jobs, max_tc, s);
+    if (e == hipSuccess && ctx->timing) e = hipEventRecord(sp.second, s);
+    if (e == hipSuccess && res_bytes)
+        e = hipMemcpyAsync(hres_v, dres, res_bytes, hipMemcpyDeviceToHost, s);
+    // the staging area is read by the queued copy: wait even after an error
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess)
+        return set_err(MH_E_DEVICE, std::string("mh_query_round_many: ") + hipGetErrorString(e));
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        const mh_round_job& j = jobs[i];
+        const size_t tc = j.tape_count;
+        const char* h = hres + jp[i].res_off;
+        if (j.first_hit && tc) std::memcpy(j.first_hit, h, tc * sizeof(uint64_t));
+        if (j.hit_count && tc)
+            std::memcpy(j.hit_count, h + tc * sizeof(uint64_t), tc * sizeof(uint64_t));
+        if (j.n_cols && tc)
+            std::memcpy(j.rows_out, h + 2 * tc * sizeof(uint64_t),
+                        tc * j.n_cols * 8 * sizeof(uint32_t));
+    }
+    return MH_OK;
 }
 
 int32_t mh_eval_values(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape, const mh_assign* as,

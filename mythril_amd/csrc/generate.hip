@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "guided_dev.h"
 #include "kernels.h"
 
@@ -18,10 +20,10 @@ using namespace mh::guided;
 constexpr int kBlock = 256;
 
 // Every column's base value written, then every set applied in order, in memory.
-__global__ void __launch_bounds__(kBlock)
-    guided_kernel(u32* assign, u64 stride, u64 first, u64 count, u64 seed, u64 base,
-                  mh::KGuide g) {
-    const u64 i = (u64)blockIdx.x * kBlock + threadIdx.x;
+// (`block` = the workgroup's row block: blockIdx.x, or a batched launch's table entry)
+__device__ __forceinline__ void guided_body(u32* assign, u64 stride, u64 first, u64 count,
+                                            u64 seed, u64 base, const mh::KGuide& g, u32 block) {
+    const u64 i = (u64)block * kBlock + threadIdx.x;
     if (i >= count) return;
     const u64 row = first + i;
     const u64 gidx = base + row;
@@ -58,10 +60,15 @@ constexpr u32 kLdsRows = 64;
 constexpr u32 kWaves = 16;  // a 256-row launch: 4 workgroups of 16 waves, 4 waves per SIMD
 constexpr size_t kGenLds = 64 * 1024;  // LDS of one generator workgroup at most
 
+__global__ void __launch_bounds__(kBlock)
+    guided_kernel(u32* assign, u64 stride, u64 first, u64 count, u64 seed, u64 base,
+                  mh::KGuide g) {
+    guided_body(assign, stride, first, count, seed, base, g, blockIdx.x);
+}
+
 template <bool STAGED>
-__global__ void __launch_bounds__(kLdsRows * kWaves)
-    guided_lds_kernel(u32* assign, u64 stride, u64 first, u64 count, u64 seed, u64 base,
-                      mh::KGuide g) {
+__device__ __forceinline__ void guided_lds_body(u32* assign, u64 stride, u64 first, u64 count,
+                                                u64 seed, u64 base, mh::KGuide g, u32 block) {
     extern __shared__ u32 s_last[];  // [n_cols][kLdsRows]: 1 + the winning entry, 0 = none
     const u32 lane = threadIdx.x % kLdsRows, wave = threadIdx.x / kLdsRows;
     for (u32 k = threadIdx.x; k < g.n_cols * kLdsRows; k += kLdsRows * kWaves) s_last[k] = 0;
@@ -74,7 +81,7 @@ __global__ void __launch_bounds__(kLdsRows * kWaves)
         g.set_prob = s_span;
     }
     __syncthreads();
-    const u64 i = (u64)blockIdx.x * kLdsRows + lane;
+    const u64 i = (u64)block * kLdsRows + lane;
     const bool live = i < count;
     const u64 row = first + (live ? i : 0);
     const u64 gidx = base + row;
@@ -113,6 +120,35 @@ __global__ void __launch_bounds__(kLdsRows * kWaves)
     }
 }
 
+template <bool STAGED>
+__global__ void __launch_bounds__(kLdsRows * kWaves)
+    guided_lds_kernel(u32* assign, u64 stride, u64 first, u64 count, u64 seed, u64 base,
+                      mh::KGuide g) {
+    guided_lds_body<STAGED>(assign, stride, first, count, seed, base, g, blockIdx.x);
+}
+
+// The batched forms (mh_query_round_many): workgroup i writes row block blocks[i].block of job
+// blocks[i].job, whose parameters come out of the device array `jobs` (read only) instead of the
+// kernel's arguments.  Every job of a launch has the launch's form (batch_plan.h gen_form) and the
+// bodies are the ones above, so a job's rows are the single-query launch's bit for bit; the
+// dynamic LDS of an LDS launch is the largest any of its jobs needs.
+__global__ void __launch_bounds__(kBlock)
+    guided_batch_kernel(const mh::GenJob* __restrict__ jobs,
+                        const mh::batch::GenEntry* __restrict__ blocks) {
+    const mh::batch::GenEntry e = blocks[blockIdx.x];
+    const mh::GenJob j = jobs[e.job];
+    guided_body(j.assign, j.stride, 0, j.count, j.seed, j.base, j.g, e.block);
+}
+
+template <bool STAGED>
+__global__ void __launch_bounds__(kLdsRows * kWaves)
+    guided_lds_batch_kernel(const mh::GenJob* __restrict__ jobs,
+                            const mh::batch::GenEntry* __restrict__ blocks) {
+    const mh::batch::GenEntry e = blocks[blockIdx.x];
+    const mh::GenJob j = jobs[e.job];
+    guided_lds_body<STAGED>(j.assign, j.stride, 0, j.count, j.seed, j.base, j.g, e.block);
+}
+
 __global__ void __launch_bounds__(kBlock)
     results_reset_kernel(u64* first_hit, u64* hit_count, u32 n) {
     const u32 i = blockIdx.x * kBlock + threadIdx.x;
@@ -133,9 +169,65 @@ __global__ void __launch_bounds__(kBlock)
     for (u32 w = threadIdx.x; w < words; w += kBlock) o[w] = hit ? assign[(u64)w * stride + row] : 0u;
 }
 
+// the batched reset and gather over the jobs' slices of one result block (kernels.h ResultJob)
+__global__ void __launch_bounds__(kBlock) results_reset_batch_kernel(const mh::ResultJob* jobs) {
+    const mh::ResultJob j = jobs[blockIdx.x];
+    for (u32 i = threadIdx.x; i < j.tc; i += kBlock) {
+        j.first_hit[i] = ~0ull;
+        j.first_hit[j.tc + i] = 0;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) witness_rows_batch_kernel(const mh::ResultJob* jobs) {
+    const mh::ResultJob j = jobs[blockIdx.y];
+    const u32 words = j.n_cols * 8;
+    u32* rows = reinterpret_cast<u32*>(j.first_hit + 2 * (u64)j.tc);
+    for (u32 t = blockIdx.x; t < j.tc; t += gridDim.x) {
+        const u64 h = j.first_hit[t];
+        const u64 row = h - j.index_base;
+        const bool hit = h != ~0ull && h >= j.index_base && row < j.stride;
+        u32* o = rows + (u64)t * words;
+        for (u32 w = threadIdx.x; w < words; w += kBlock)
+            o[w] = hit ? j.assign[(u64)w * j.stride + row] : 0u;
+    }
+}
+
 }  // namespace
 
 namespace mh {
+
+hipError_t launch_generate_guided_batch(const GenJob* jobs, const batch::GenEntry* blocks,
+                                        uint32_t n_blocks, uint32_t form, uint64_t lds_bytes,
+                                        hipStream_t stream) {
+    if (n_blocks == 0) return hipSuccess;
+    if (lds_bytes > kGenLds) return hipErrorInvalidValue;
+    if (form == batch::kFormStaged)
+        hipLaunchKernelGGL(guided_lds_batch_kernel<true>, dim3(n_blocks), dim3(kLdsRows * kWaves),
+                           (size_t)lds_bytes, stream, jobs, blocks);
+    else if (form == batch::kFormLds)
+        hipLaunchKernelGGL(guided_lds_batch_kernel<false>, dim3(n_blocks), dim3(kLdsRows * kWaves),
+                           (size_t)lds_bytes, stream, jobs, blocks);
+    else if (form == batch::kFormMem)
+        hipLaunchKernelGGL(guided_batch_kernel, dim3(n_blocks), dim3(kBlock), 0, stream, jobs,
+                           blocks);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_results_reset_batch(const ResultJob* jobs, uint32_t n_jobs, hipStream_t stream) {
+    if (n_jobs == 0) return hipSuccess;
+    hipLaunchKernelGGL(results_reset_batch_kernel, dim3(n_jobs), dim3(kBlock), 0, stream, jobs);
+    return hipGetLastError();
+}
+
+hipError_t launch_witness_rows_batch(const ResultJob* jobs, uint32_t n_jobs, uint32_t max_tc,
+                                     hipStream_t stream) {
+    if (n_jobs == 0 || max_tc == 0) return hipSuccess;
+    hipLaunchKernelGGL(witness_rows_batch_kernel, dim3(std::min<uint32_t>(max_tc, 16), n_jobs),
+                       dim3(kBlock), 0, stream, jobs);
+    return hipGetLastError();
+}
 
 hipError_t launch_results_reset(uint64_t* first_hit, uint64_t* hit_count, uint32_t n,
                                 hipStream_t stream) {
@@ -159,13 +251,15 @@ hipError_t launch_generate_guided(uint32_t* assign, uint64_t stride, uint64_t fi
                                   hipStream_t stream) {
     if (count == 0) return hipSuccess;
     // LDS form while the last-entry slots (256 B per column) fit 48 KB per workgroup
-    const size_t lds = (size_t)g.n_cols * kLdsRows * sizeof(u32);
-    const size_t staged = lds + (size_t)g.span_words * sizeof(u32);
+    // (batch_plan.h gen_form: the rule the batched launches pick a job's form by)
+    const size_t lds = (size_t)mh::batch::gen_lds_bytes(g.n_cols);
+    const size_t staged = (size_t)mh::batch::gen_staged_bytes(g.n_cols, g.span_words);
     const u64 blocks = (count + kLdsRows - 1) / kLdsRows;
-    if (g.n_cols && staged <= kGenLds) {
+    const mh::batch::GenForm form = mh::batch::gen_form(g.n_cols, g.span_words);
+    if (form == mh::batch::kFormStaged) {
         hipLaunchKernelGGL(guided_lds_kernel<true>, dim3((unsigned)blocks), dim3(kLdsRows * kWaves),
                            staged, stream, assign, stride, first, count, seed, base, g);
-    } else if (g.n_cols && lds <= 48 * 1024) {
+    } else if (form == mh::batch::kFormLds) {
         hipLaunchKernelGGL(guided_lds_kernel<false>, dim3((unsigned)blocks), dim3(kLdsRows * kWaves),
                            lds, stream, assign, stride, first, count, seed, base, g);
     } else {

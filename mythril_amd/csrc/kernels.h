@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/mythril_hip.h"
+#include "batch_plan.h"
 #include "dev_isa.h"
 
 namespace mh {
@@ -80,6 +81,35 @@ struct KGuide {
 hipError_t launch_generate_guided(uint32_t* assign, uint64_t stride, uint64_t first,
                                   uint64_t count, uint64_t seed, uint64_t base, const KGuide& g,
                                   hipStream_t stream);
+// A batched round (mh_query_round_many; the tables are batch_plan.h's, on the device, read only).
+// Interpreter: workgroup i of the launch runs blocks[i] = {segment, row block, tape slice, slices}
+// with segs[segment]; `variant` < kFirstTableVariant serves every segment of the launch.
+hipError_t launch_sieve_batch(const KParams* segs, const batch::BlockEntry* blocks,
+                              uint32_t n_blocks, uint32_t variant, hipStream_t stream);
+// Generator: what launch_generate_guided takes, per job (rows [0, count) of the buffer).
+struct GenJob {
+    uint32_t* assign;
+    uint64_t stride, count, seed, base;
+    KGuide g;
+};
+// workgroup i writes row block blocks[i].block of jobs[blocks[i].job] with the kernel of `form`
+// (batch::GenForm: every job of the launch has that form, batch::gen_form)
+hipError_t launch_generate_guided_batch(const GenJob* jobs, const batch::GenEntry* blocks,
+                                        uint32_t n_blocks, uint32_t form, uint64_t lds_bytes,
+                                        hipStream_t stream);
+// One job's slice of the batch's device result block, first_hit[tc] | hit_count[tc] |
+// rows[tc][n_cols][8], and the buffer its witness rows are read from.
+struct ResultJob {
+    uint64_t* first_hit;     // hit_count = first_hit + tc, rows = first_hit + 2 tc
+    const uint32_t* assign;
+    uint64_t stride, index_base;
+    uint32_t tc, n_cols;
+};
+// every job's first_hit = MH_NO_HIT and hit_count = 0: one launch, a workgroup per job
+hipError_t launch_results_reset_batch(const ResultJob* jobs, uint32_t n_jobs, hipStream_t stream);
+// every job's witness rows (launch_witness_rows per job): one launch, grid (tapes, jobs)
+hipError_t launch_witness_rows_batch(const ResultJob* jobs, uint32_t n_jobs, uint32_t max_tc,
+                                     hipStream_t stream);
 // first_hit[0..n) = MH_NO_HIT, hit_count[0..n) = 0 in one launch (either may be null)
 hipError_t launch_results_reset(uint64_t* first_hit, uint64_t* hit_count, uint32_t n,
                                 hipStream_t stream);

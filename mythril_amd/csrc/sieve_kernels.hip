@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "batch_plan.h"
 #include "dev_isa.h"
 #include "exec.h"
 #include "kernels.h"
@@ -257,26 +258,42 @@ __device__ __forceinline__ InsnCache lds_insns(const uint2* s_insn, u32 off, u32
     return c;
 }
 
-template <int NR, int FEAT, int BLOCK>
-__device__ __forceinline__ void sieve_body(const KParams& p) {
+// The workgroup's block coordinates, an argument of sieve_body: bx = its row block, by of ny = its
+// slice of the tape list.  sieve_kernel's are the grid's, read where the body uses them (its
+// code is what it was when the body named blockIdx itself); sieve_batch_kernel's come out of a
+// block-table entry.
+struct GridCoords {
+    __device__ __forceinline__ u32 bx() const { return blockIdx.x; }
+    __device__ __forceinline__ u32 by() const { return blockIdx.y; }
+    __device__ __forceinline__ u32 ny() const { return gridDim.y; }
+};
+struct TableCoords {
+    u32 x, y, n;
+    __device__ __forceinline__ u32 bx() const { return x; }
+    __device__ __forceinline__ u32 by() const { return y; }
+    __device__ __forceinline__ u32 ny() const { return n; }
+};
+
+template <int NR, int FEAT, int BLOCK, class Coords>
+__device__ __forceinline__ void sieve_body(const KParams& p, const Coords at) {
     __shared__ uint2 s_insn[kLdsInsns];
     __shared__ u32 s_off[kChunk], s_n[kChunk], s_rb[kChunk], s_tid[kChunk];
     __shared__ u32 s_meta[4];  // tapes in chunk, first word index, words, streaming flag
     __shared__ unsigned long long s_min[kChunk];
     __shared__ unsigned long long s_cnt[kChunk];
     const u32 tid = threadIdx.x;
-    const u64 row = p.row_first + (u64)blockIdx.x * BLOCK + tid;
+    const u64 row = p.row_first + (u64)at.bx() * BLOCK + tid;
     const bool valid = row < p.row_first + p.row_count;
     DevMachine<NR> m;
     m.p = &p;
     m.lrow = valid ? row : p.row_first;
     preload<NR>(m, p);
-    const u64 block_first = p.index_base + p.row_first + (u64)blockIdx.x * BLOCK;
+    const u64 block_first = p.index_base + p.row_first + (u64)at.bx() * BLOCK;
     const u64 wave_first = block_first + (tid & ~63u);
     // grid y splits the tape list (a short run -- a query's 256-row first round is one
     // workgroup -- spreads its tapes over CUs instead of running them all on one)
-    const u32 id_lo = (u32)((u64)p.n_ids * blockIdx.y / gridDim.y);
-    const u32 n_ids = (u32)((u64)p.n_ids * (blockIdx.y + 1) / gridDim.y) - id_lo;
+    const u32 id_lo = (u32)((u64)p.n_ids * at.by() / at.ny());
+    const u32 n_ids = (u32)((u64)p.n_ids * (at.by() + 1) / at.ny()) - id_lo;
     const u32* tape_ids = p.tape_ids + id_lo;
     for (u32 cb = 0; cb < n_ids;) {
         __syncthreads();  // previous chunk's LDS fully consumed
@@ -358,7 +375,7 @@ __device__ __forceinline__ void sieve_body(const KParams& p) {
                 if (p.masks) {  // a part of a split tape: its wave mask, combined later
                     if ((tid & 63u) == 0) {
                         const u32 t = __builtin_amdgcn_readfirstlane(s_tid[j]);
-                        const u64 w = ((u64)blockIdx.x * BLOCK + (tid & ~63u)) / 64u;
+                        const u64 w = ((u64)at.bx() * BLOCK + (tid & ~63u)) / 64u;
                         p.masks[(u64)(t - p.mask_base) * p.mask_stride + w] = mask;
                     }
                 } else if (mask && (tid & 63u) == 0) {
@@ -664,7 +681,32 @@ constexpr int sieve_min_waves(int nr, int feat) {
 template <int NR, int FEAT, int BLOCK>
 __global__ void __launch_bounds__(BLOCK)
 __attribute__((amdgpu_waves_per_eu(sieve_min_waves(NR, FEAT), 8))) sieve_kernel(const KParams p) {
-    sieve_body<NR, FEAT, BLOCK>(p);
+    sieve_body<NR, FEAT, BLOCK>(p, GridCoords{});
+}
+
+// Many short runs in one launch (mh_query_round_many): sieve_body driven by a block table instead
+// of blockIdx and one by-value KParams.  Workgroup i is entry i of `blocks`, {segment, row block,
+// tape slice, slices} (batch_plan.h), and runs the segment's KParams out of the device array
+// `segs` -- one query's tapes of one register class over its own rows, results and first_hit
+// array.  Both tables are read only, at wave-uniform addresses before any store of the kernel,
+// so the loads are scalar and the parameters live in SGPRs as a kernel argument's do; the body
+// -- LDS chunking, the FIRST_HIT early exit, one atomic per tape per workgroup -- is unchanged.
+// One-wave workgroups: the short-run shape sieve_block() picks for <= kShortRows rows.
+template <int NR, int FEAT>
+__global__ void __launch_bounds__(64)
+__attribute__((amdgpu_waves_per_eu(sieve_min_waves(NR, FEAT), 8)))
+sieve_batch_kernel(const KParams* __restrict__ segs, const mh::batch::BlockEntry* __restrict__ blocks) {
+    const mh::batch::BlockEntry e = blocks[blockIdx.x];
+    const KParams p = segs[e.seg];
+    sieve_body<NR, FEAT, 64>(p, TableCoords{e.block, e.y, e.ny});
+}
+
+template <int NR, int FEAT>
+hipError_t launch_batch_variant(const KParams* segs, const mh::batch::BlockEntry* blocks,
+                                uint32_t n_blocks, hipStream_t stream) {
+    hipLaunchKernelGGL((sieve_batch_kernel<NR, FEAT>), dim3(n_blocks), dim3(64), 0, stream, segs,
+                       blocks);
+    return hipGetLastError();
 }
 
 // one workgroup per split tape: the AND of its parts' wave masks (kernels.h launch_combine)
@@ -750,6 +792,27 @@ hipError_t launch_sieve(const KParams& p, uint32_t variant, hipStream_t stream) 
         case 12: return launch_variant<MH_NR_SMALL, kTab>(p, stream);
         case 13: return launch_variant<MH_NR_MID, kTab>(p, stream);
         case 14: return launch_variant<MH_NR_MAX, kTab>(p, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_sieve_batch(const KParams* segs, const batch::BlockEntry* blocks,
+                              uint32_t n_blocks, uint32_t variant, hipStream_t stream) {
+    if (n_blocks == 0) return hipSuccess;
+    constexpr int kCplx = F_CPLX, kKec = F_CPLX | F_KECCAK, kAll = F_CPLX | F_KECCAK | F_EVM;
+    switch (variant) {  // the twelve non-table variants: a batch never holds a lookup
+        case 0: return launch_batch_variant<MH_NR_SMALL, 0>(segs, blocks, n_blocks, stream);
+        case 1: return launch_batch_variant<MH_NR_SMALL, kCplx>(segs, blocks, n_blocks, stream);
+        case 2: return launch_batch_variant<MH_NR_SMALL, kKec>(segs, blocks, n_blocks, stream);
+        case 3: return launch_batch_variant<MH_NR_SMALL, kAll>(segs, blocks, n_blocks, stream);
+        case 4: return launch_batch_variant<MH_NR_MID, 0>(segs, blocks, n_blocks, stream);
+        case 5: return launch_batch_variant<MH_NR_MID, kCplx>(segs, blocks, n_blocks, stream);
+        case 6: return launch_batch_variant<MH_NR_MID, kKec>(segs, blocks, n_blocks, stream);
+        case 7: return launch_batch_variant<MH_NR_MID, kAll>(segs, blocks, n_blocks, stream);
+        case 8: return launch_batch_variant<MH_NR_MAX, 0>(segs, blocks, n_blocks, stream);
+        case 9: return launch_batch_variant<MH_NR_MAX, kCplx>(segs, blocks, n_blocks, stream);
+        case 10: return launch_batch_variant<MH_NR_MAX, kKec>(segs, blocks, n_blocks, stream);
+        case 11: return launch_batch_variant<MH_NR_MAX, kAll>(segs, blocks, n_blocks, stream);
         default: return hipErrorInvalidValue;
     }
 }

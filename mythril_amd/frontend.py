@@ -35,6 +35,7 @@ import inspect
 import logging
 import threading
 import time
+from collections import OrderedDict
 from functools import lru_cache
 from pathlib import Path
 from typing import Callable, Optional
@@ -91,6 +92,7 @@ def configure(*, fallback: Optional[Callable] = None, verify: Optional[Callable]
     if sieve_kwargs:
         _config["sieve_kwargs"] = dict(sieve_kwargs)
         close_sieve()
+    clear_prefetched()
     get_model.cache_clear()
 
 
@@ -123,6 +125,7 @@ def reset() -> None:
     _config.update(fallback=None, verify=None, to_terms=None, log_writer=None,
                    fallback_logs=False, sieve_kwargs={}, enabled=True, certify=None)
     close_sieve()
+    clear_prefetched()
     get_model.cache_clear()
 
 
@@ -155,6 +158,7 @@ def forget_witnesses() -> None:
     s = getattr(_tls, "sieve", None)
     if s is not None:
         s.witnesses.clear()
+    clear_prefetched()  # (keyed by the same node ids)
 
 
 def close_sieve() -> None:
@@ -208,6 +212,76 @@ def _terms(constraints):
     return conv(constraints)
 
 
+PARKED_MAX = 4096  # answers prefetch() keeps per thread, oldest dropped
+
+
+def _parked() -> "OrderedDict":
+    """This thread's parked answers (prefetch): key -> (term context, witness or None, the
+    sieve's last_miss, its last_rounds)."""
+    t = getattr(_tls, "parked", None)
+    if t is None:
+        t = _tls.parked = OrderedDict()
+    return t
+
+
+def clear_prefetched() -> None:
+    """Drop this thread's parked answers (configure, reset, forget_witnesses do)."""
+    t = getattr(_tls, "parked", None)
+    if t:
+        t.clear()
+
+
+def prefetch(queries) -> int:
+    """Solve many feasibility queries ahead of the get_model calls that will ask them, with
+    their first rounds in one device submission (Sieve.solve_many): ``queries`` is an iterable of
+    constraint tuples, as get_model takes them -- LASER asks every open world state's
+    constraints at the start of a transaction round (laser/ethereum/svm.py:201-203).  Each
+    answer is parked under the query's key; sieve_model looks there before it runs a round of
+    its own: a parked witness goes through certification and the verifier as any other, a parked
+    miss goes to the fallback without a device round (and the fallback's model is still
+    learnt).  A query with a Python False is UNSAT without the sieve and is skipped; other bools
+    are dropped, as in get_model.  The whole list shares args.solver_timeout.  Never raises: any
+    error leaves the table as it was and the queries to the ordinary path.  Returns the number
+    of answers parked."""
+    try:
+        if not _config["enabled"]:
+            return 0
+        s = sieve()
+        table = _parked()
+        items, seen = [], set()
+        for q in queries:
+            cs = tuple(q)
+            if any(type(c) == bool and not c for c in cs):
+                continue
+            cs = [c for c in cs if type(c) != bool]
+            if not cs:
+                continue
+            ctx, terms = _terms(cs)
+            key = tuple(t.node for t in terms)
+            if key in seen or (key in table and table[key][0] is ctx):
+                continue
+            seen.add(key)
+            items.append((ctx, key))
+        # (an importer that replaced its term context on the way has made the earlier keys stale)
+        items = [it for it in items if it[0] is items[-1][0]]
+        if not items:
+            return 0
+        out = s.solve_many([ctx.b for ctx, _ in items], [list(key) for _, key in items],
+                           keys=[key for _, key in items],
+                           budget_s=max(args.solver_timeout, 0.0) / 1000.0)
+        fresh = [(key, (ctx, w, rec["miss"], rec["rounds"]))
+                 for (ctx, key), w, rec in zip(items, out, s.last_many) if rec["error"] is None]
+    except Exception as e:  # noqa: BLE001 - prefetching never changes an answer
+        log.debug("prefetch left to the ordinary path: %s", e)
+        return 0
+    for key, entry in fresh:
+        table[key] = entry
+        table.move_to_end(key)
+    while len(table) > PARKED_MAX:
+        table.popitem(last=False)
+    return len(fresh)
+
+
 def sieve_model(constraints, timeout_ms: Optional[float] = None):
     """The sieve's answer for a feasibility query: a Model, or None (ask the fallback).
     ``timeout_ms`` is get_model's budget (support/model.py:26-31): the sieve's own rounds and the
@@ -222,7 +296,14 @@ def sieve_model(constraints, timeout_ms: Optional[float] = None):
         ctx, terms = _terms(constraints)
         key = tuple(t.node for t in terms)
         budget = None if timeout_ms is None else max(timeout_ms, 0.0) / 1000.0
-        w = s.solve(ctx.b, [t.node for t in terms], key=key, budget_s=budget)
+        parked = getattr(_tls, "parked", None)
+        entry = parked.pop(key, None) if parked else None
+        if entry is not None and entry[0] is ctx:
+            # answered by prefetch(): no round here; a miss leaves the sieve as solve() would
+            # have, so the fallback's model of it is learnt
+            _, w, s.last_miss, s.last_rounds = entry
+        else:
+            w = s.solve(ctx.b, [t.node for t in terms], key=key, budget_s=budget)
     except Exception as e:  # fail closed: any problem means "ask the fallback"
         from .lower import LoweringUnsupported
         from .native import Unsupported

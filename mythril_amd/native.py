@@ -73,6 +73,7 @@ SIGNATURES = {
     "mh_query_round": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64,
                                    C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p, C.c_uint32,
                                    _u32p]),
+    "mh_query_round_many": (C.c_int32, [_vp, _vp, C.c_uint32]),
     "mh_run_async": (C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint64,
                                  C.c_uint64, C.c_uint32, _vp, _vp]),
     "mh_eval_values": (C.c_int32, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint64, _u32p]),
@@ -226,6 +227,20 @@ class Guide(C.Structure):
         ("entry_val", _u32p),
     ]
 
+
+class RoundJob(C.Structure):
+    """mh_round_job (include/mythril_hip.h)."""
+
+    _fields_ = [
+        ("ts", _vp), ("as_", _vp), ("guide", C.POINTER(Guide)),
+        ("seed", C.c_uint64), ("global_base", C.c_uint64), ("count", C.c_uint64),
+        ("tape_first", C.c_uint32), ("tape_count", C.c_uint32), ("mode", C.c_uint32),
+        ("n_cols", C.c_uint32),
+        ("first_hit", _u64p), ("hit_count", _u64p), ("rows_out", _u32p),
+    ]
+
+
+ROUND_MANY_MAX = 256  # MH_ROUND_MANY_MAX
 
 _lib: Optional[C.CDLL] = None
 
@@ -1095,6 +1110,35 @@ def query_round(ctx: Context, tapes: CompiledTapes, assign: "Assignments", guide
                                   global_base, count, tape_first, tc, mode, _ptr(fh, C.c_uint64),
                                   _ptr(hc, C.c_uint64), n_cols, _ptr(rows)))
     return fh[:tc], hc[:tc], rows[:tc, :n_cols]
+
+
+def query_round_many(ctx: Context, jobs: Sequence[dict]):
+    """Many guided rounds in one device submission (mh_query_round_many).  Each job is a dict
+    of query_round's arguments: tapes, assign, guide, seed, global_base, count, n_cols and
+    optionally tape_first, tape_count, mode.  Returns per job (first_hit, hit_count, rows), each
+    equal to what query_round returns for the job alone; lists beyond ROUND_MANY_MAX jobs go
+    up in chunks."""
+    out = []
+    for lo in range(0, len(jobs), ROUND_MANY_MAX):
+        chunk = jobs[lo:lo + ROUND_MANY_MAX]
+        arr = (RoundJob * len(chunk))()
+        res = []
+        for k, j in enumerate(chunk):
+            tapes, n_cols = j["tapes"], j["n_cols"]
+            tf = j.get("tape_first", 0)
+            tc = j.get("tape_count")
+            tc = tapes.n_tapes - tf if tc is None else tc
+            fh = np.zeros(max(tc, 1), dtype=np.uint64)
+            hc = np.zeros(max(tc, 1), dtype=np.uint64)
+            rows = np.zeros((max(tc, 1), max(n_cols, 1), 8), dtype=np.uint32)
+            arr[k] = RoundJob(tapes.h, j["assign"].h, C.pointer(j["guide"].guide), j["seed"],
+                              j["global_base"], j["count"], tf, tc,
+                              j.get("mode", MODE_FIRST_HIT), n_cols, _ptr(fh, C.c_uint64),
+                              _ptr(hc, C.c_uint64), _ptr(rows))
+            res.append((fh, hc, rows, tc, n_cols))
+        _check(ctx.lib.mh_query_round_many(ctx.h, arr, len(chunk)))
+        out.extend((fh[:tc], hc[:tc], rows[:tc, :n_cols]) for fh, hc, rows, tc, n_cols in res)
+    return out
 
 
 def run_async(ctx: Context, tapes: CompiledTapes, assign: Assignments, d_first_hit: int,

@@ -196,14 +196,32 @@ def z3_verifier(constraints, model, timeout_ms=None):
 class SievePlugin(LaserPlugin):
     """LaserPlugin: installs the sieve front end for one symbolic execution."""
 
-    def __init__(self, modules: Optional[Sequence[object]] = None, **sieve_kwargs):
+    def __init__(self, modules: Optional[Sequence[object]] = None,
+                 prefetch: Optional[bool] = None, **sieve_kwargs):
         self.modules = modules
         self.sieve_kwargs = sieve_kwargs
         self.installation = Installation()
+        # prefetch=True (or SIEVE_PREFETCH=1; off by default): after every transaction the open
+        # world states' constraints -- the queries the next round's filter is about to ask one
+        # by one (laser/ethereum/svm.py:201-203) -- are solved in one batch (frontend.prefetch)
+        if prefetch is None:
+            import os
+
+            prefetch = os.environ.get("SIEVE_PREFETCH", "0") == "1"
+        self.prefetch = bool(prefetch)
 
     def initialize(self, symbolic_vm) -> None:
         symbolic_vm.register_laser_hooks("start_sym_exec", self.start)
         symbolic_vm.register_laser_hooks("stop_sym_exec", self.stop)
+        if self.prefetch:
+            symbolic_vm.register_laser_hooks(
+                "stop_sym_trans", lambda: self.prefetch_open_states(symbolic_vm))
+
+    @staticmethod
+    def prefetch_open_states(symbolic_vm) -> int:
+        """The stop_sym_trans hook: the open states' path conditions, as is_possible will ask
+        them (state/constraints.py:26-35: get_model(tuple(constraints)))."""
+        return frontend.prefetch(tuple(s.constraints) for s in symbolic_vm.open_states)
 
     def start(self) -> None:
         modules = self.modules if self.modules is not None else _reference_modules()

@@ -416,6 +416,25 @@ def rematerialize(nodes: np.ndarray, max_size: int) -> np.ndarray:
     return np.array(out, dtype=nodes.dtype)
 
 
+class _Staged:
+    """A query after its host stage (Sieve._stage), before its rounds (Sieve._rounds): the
+    lowering, the parent witness it was harvested under, the kept guide and the compiled tapes."""
+
+    __slots__ = ("b", "key", "keccak_reads", "base_schema", "qno", "host", "col_index", "parent",
+                 "parent_len", "guide", "ct", "t1")
+
+    def __init__(self, b, key, keccak_reads, base_schema, qno, host, col_index, parent,
+                 parent_len, guide, ct, t1):
+        self.b, self.key, self.keccak_reads, self.base_schema = b, key, keccak_reads, base_schema
+        self.qno, self.host, self.col_index = qno, host, col_index
+        self.parent, self.parent_len, self.guide, self.ct, self.t1 = (parent, parent_len, guide,
+                                                                      ct, t1)
+
+    def close(self) -> None:  # a staged query whose rounds never ran
+        self.ct.close()
+        self.guide.close()
+
+
 class Sieve:
     """A device context plus reusable buffers; one per thread (handles are not shared)."""
 
@@ -520,6 +539,10 @@ class Sieve:
             os.environ.get("SIEVE_REPAIR_SCORE_ROWS", "4096"))))
         self.repairer = None                                  # native.Repair, made on first use
         self.assign2: Optional[native.Assignments] = None     # the children's buffer
+        # solve_many: first-round buffers (first_rows rows) by column capacity, kept between
+        # calls; and the last call's per-query records
+        self.round_pool: Dict[int, List[native.Assignments]] = {}
+        self.last_many: List[Dict] = []
 
     def close(self) -> None:
         if self.repairer is not None:
@@ -531,6 +554,10 @@ class Sieve:
         if self.assign is not None:
             self.assign.close()
             self.assign = None
+        for bufs in self.round_pool.values():
+            for a in bufs:
+                a.close()
+        self.round_pool = {}
         self.guides.close()
         if self.guides_kr is not None:
             self.guides_kr.close()
@@ -828,22 +855,34 @@ class Sieve:
         if budget <= 0:
             self.stats.misses += 1
             return None
+        qno = self.stats.queries
+        staged = self._stage(b, roots, key, False, qno)
+        return self._finish(b, roots, key, qno, staged, None, budget, t0)
+
+    def _finish(self, b: TapeBuilder, roots: Sequence[int], key: Optional[tuple], qno: int,
+                staged, first, budget: float, t0: float) -> Optional[Witness]:
+        """A query from its host stage on (``staged``: _stage's result): the rounds, the keccak
+        second chance and the accounting of the answer.  ``first``: its first round's results when
+        a batched round (solve_many) has run it already."""
         st = self.stats
-        w, schema, kec = self._attempt(b, roots, key, budget, t0, False)
+        if staged is REFUTED:
+            w, schema, kec = None, REFUTED, False
+        else:
+            w, schema, kec = self._rounds(staged, budget, t0, first)
         schema2 = None
         if (w is None and kec and self.keccak_second_chance
                 and time.perf_counter() - t0 < budget):
             st.extra["keccak2_tries"] = st.extra.get("keccak2_tries", 0) + 1
-            first = self.last_rounds
+            first_rounds = self.last_rounds
             try:
                 w, schema2, _ = self._attempt(b, roots, key, budget, t0, True,
-                                              base_schema=schema)
+                                              base_schema=schema, qno=qno)
             except (LoweringUnsupported, native.Unsupported):
                 # a shape the second lowering cannot take (register pressure of its larger
                 # tapes, ...): the first attempt's miss stands
                 st.extra["keccak2_unsupported"] = st.extra.get("keccak2_unsupported", 0) + 1
                 w = None
-            self.last_rounds = dict(first, keccak2=int(w is not None))
+            self.last_rounds = dict(first_rounds, keccak2=int(w is not None))
             if w is not None:
                 st.extra["keccak2_hits"] = st.extra.get("keccak2_hits", 0) + 1
         if w is None:
@@ -856,6 +895,156 @@ class Sieve:
             self.remember(key, w)
         self.stats.hits += 1
         return w
+
+    # queries per batched round: each has a first-round buffer of its own (first_rows rows by its
+    # columns, 8 MiB at 64 columns), so the pool stays within half a GiB
+    BATCH_MAX = 64
+
+    def _pool_buffer(self, n_cols: int, taken: Dict[int, int]) -> native.Assignments:
+        """A first-round buffer from the pool, of _buffer's column capacity; `taken` counts the
+        ones this batch uses already."""
+        cap = max(n_cols, 64)
+        cap = 1 << (cap - 1).bit_length()
+        bufs = self.round_pool.setdefault(cap, [])
+        k = taken.get(cap, 0)
+        taken[cap] = k + 1
+        if k == len(bufs) or bufs[k].capacity < self.first_rows:
+            a = self.ctx.assignments(cap, self.first_rows)
+            if k == len(bufs):
+                bufs.append(a)
+            else:
+                bufs[k].close()
+                bufs[k] = a
+        return bufs[k]
+
+    def solve_many(self, b, queries: Sequence[Sequence[int]],
+                   keys: Optional[Sequence[Optional[tuple]]] = None,
+                   budget_s: Optional[float] = None) -> List[Optional[Witness]]:
+        """solve() for a list of independent queries of builder `b` (or of one builder per query,
+        given as a list), with the first round of
+        every query that needs one run in one device submission (native.query_round_many)
+        instead of one submission each.  Returns a witness or None per query; ``last_many`` has,
+        per query, ``miss`` (what last_miss would have been), ``rounds`` (last_rounds) and
+        ``error`` (the exception an unsupported query raises from solve(), reported here instead:
+        it does not fail the list).
+
+        On Sieves created alike, the witnesses, their ``index`` and ``rounds``, the stats counters
+        and the ``witnesses`` store are what calling solve() on the list in order gives:
+        query numbers (the generator's global_base) go by list position; a query whose parent key
+        (within ANCESTORS) is an earlier query's key in the list starts a new batch, after that
+        one has finished, so it is harvested under the same parent witness; every later round
+        (incremental, second_round, keccak second chance, repair) runs one query at a time as in
+        solve().  An exact duplicate (same key and roots) of an earlier query in the list is not
+        solved again: it takes a query number and the earlier one's answer.  ``budget_s`` is the
+        whole list's budget; a query not started when it is spent is a miss."""
+        t0 = time.perf_counter()
+        budget = self.budget_s if budget_s is None else min(self.budget_s, budget_s)
+        n = len(queries)
+        # (one builder for the list, or one per query: paths built in contexts of their own)
+        bs = list(b) if isinstance(b, (list, tuple)) else [b] * n
+        if len(bs) != n:
+            raise ValueError("solve_many: one builder, or one per query")
+        keys = list(keys) if keys is not None else [None] * n
+        if len(keys) != n:
+            raise ValueError("solve_many: one key (or None) per query")
+        out: List[Optional[Witness]] = [None] * n
+        rec: List[Dict] = [dict(miss=None, rounds={}, error=None) for _ in range(n)]
+        self.last_many = rec
+        st = self.stats
+        ident = [(id(bs[i]), keys[i], tuple(queries[i])) for i in range(n)]
+        seen: Dict[tuple, int] = {}
+        i = 0
+        while i < n:
+            # the next batch: queries up to one that must see an earlier one's witness
+            seg_keys, seg, dups = set(), [], []
+            j = i
+            while j < n and len(seg) < self.BATCH_MAX:
+                k = keys[j]
+                if k and any(k[:m] in seg_keys
+                             for m in range(len(k) - 1, max(len(k) - 1 - self.ANCESTORS, 0), -1)):
+                    break
+                if ident[j] in seen:
+                    dups.append((j, seen[ident[j]]))
+                else:
+                    seen[ident[j]] = j
+                    seg.append(j)
+                    if k:
+                        seg_keys.add(k)
+                j += 1
+            staged: Dict[int, object] = {}
+            try:
+                # 1. numbers and host stages, in list order
+                qnos = {}
+                for q in sorted(seg + [d for d, _ in dups]):
+                    st.queries += 1
+                    qnos[q] = st.queries
+                for q in seg:
+                    if budget <= 0 or time.perf_counter() - t0 >= budget:
+                        st.misses += 1
+                        continue
+                    try:
+                        staged[q] = self._stage(bs[q], queries[q], keys[q], False, qnos[q])
+                    except Exception as e:  # noqa: BLE001 - what solve() raises, per query
+                        rec[q]["error"] = e
+                # 2. one submission for every first round
+                live = [q for q in seg if q in staged and staged[q] is not REFUTED]
+                firsts: Dict[int, tuple] = {}
+                if len(live) > 1:
+                    taken: Dict[int, int] = {}
+                    jobs = []
+                    for q in live:
+                        s = staged[q]
+                        n_cols = len(s.host[0])
+                        jobs.append(dict(tapes=s.ct, assign=self._pool_buffer(n_cols, taken),
+                                         guide=s.guide, seed=self.seed, global_base=s.qno << 24,
+                                         count=self.first_rows, n_cols=n_cols,
+                                         mode=native.MODE_FIRST_HIT))
+                    tb = time.perf_counter()
+                    try:
+                        res = native.query_round_many(self.ctx, jobs)
+                    except native.SieveError:  # (a shape the batch refuses: one by one instead)
+                        st.extra["batch_refused"] = st.extra.get("batch_refused", 0) + 1
+                        res = None
+                    st.add("run", time.perf_counter() - tb)
+                    if res is not None:
+                        st.extra["batched_rounds"] = st.extra.get("batched_rounds", 0) + len(live)
+                        st.extra["batches"] = st.extra.get("batches", 0) + 1
+                        for q, job, (fh, _, wrows) in zip(live, jobs, res):
+                            firsts[q] = (fh, wrows, job["assign"])
+                # 3. every query's later rounds and accounting, in list order
+                dup_of = dict(dups)
+                for q in range(i, j):
+                    if q in dup_of:  # the earlier query's answer, accounted and stored again
+                        orig = dup_of[q]
+                        out[q] = out[orig]
+                        rec[q] = dict(rec[orig])
+                        if rec[orig]["error"] is None:
+                            if out[orig] is None:
+                                st.misses += 1
+                            else:
+                                st.hits += 1
+                                if keys[q]:
+                                    self.remember(keys[q], out[orig])
+                        continue
+                    if q not in staged:
+                        continue
+                    s = staged.pop(q)
+                    self.last_rounds = {}
+                    self.last_miss = None
+                    try:
+                        out[q] = self._finish(bs[q], queries[q], keys[q], qnos[q], s, firsts.get(q),
+                                              budget, t0)
+                    except Exception as e:  # noqa: BLE001
+                        rec[q]["error"] = e
+                    rec[q]["miss"], rec[q]["rounds"] = self.last_miss, self.last_rounds
+            finally:
+                for s in staged.values():  # an interrupted batch: nothing stays open
+                    if s is not REFUTED:
+                        s.close()
+            i = j
+        self.last_rounds = {}
+        self.last_miss = None
+        return out
 
     def _guide_session(self, keccak_reads: bool) -> "native.GuideSession":
         """The harvester session of a lowering mode (each keeps its own path's memo)."""
@@ -913,16 +1102,30 @@ class Sieve:
 
     def _attempt(self, b: TapeBuilder, roots: Sequence[int], key: Optional[tuple],
                  budget: float, t0: float, keccak_reads: bool,
-                 base_schema: Optional[Schema] = None):
+                 base_schema: Optional[Schema] = None, qno: Optional[int] = None):
         """One lowering of the query and its rounds: (witness or None, schema or REFUTED,
         whether a group left unsolved reads a keccak application).  ``base_schema``: the
-        default lowering's schema, for the second chance's incremental round."""
+        default lowering's schema, for the second chance's incremental round.  The host stage
+        (_stage), then the rounds (_rounds)."""
+        staged = self._stage(b, roots, key, keccak_reads,
+                             self.stats.queries if qno is None else qno, base_schema)
+        if staged is REFUTED:
+            return None, REFUTED, False
+        return self._rounds(staged, budget, t0)
+
+    def _stage(self, b: TapeBuilder, roots: Sequence[int], key: Optional[tuple],
+               keccak_reads: bool, qno: int, base_schema: Optional[Schema] = None):
+        """The host stage of one lowering of a query: native build (REFUTED when the query
+        contradicts itself: no device round), guide harvest and tape compile.  ``qno``: the
+        query's number (stats.queries when sequential solve reaches it), which its rounds'
+        global_base is made of.  The result owns the guide and the compiled tapes until _rounds
+        (or its close()) releases them."""
         st = self.stats
         th = time.perf_counter()
         host = self._host_native(b, roots, keccak_reads) if self.native_query else None
         if host is REFUTED:  # no witness exists: no device round (the fallback still runs)
             self.stats.host_s += time.perf_counter() - th
-            return None, REFUTED, False
+            return REFUTED
         if host is None:
             host = self._host_python(b, roots, keccak_reads)
         columns, widths, schema, root_nodes, ts, group_cols, defs, root_ends = host
@@ -963,6 +1166,19 @@ class Sieve:
         except BaseException:
             guide.close()
             raise
+        return _Staged(b, key, keccak_reads, base_schema, qno, host, col_index, parent, parent_len,
+                       guide, ct, t1)
+
+    def _rounds(self, s: "_Staged", budget: float, t0: float, first=None):
+        """The rounds of a staged query: (witness or None, schema, whether a group left unsolved
+        reads a keccak application).  ``first`` = (first_hit, witness rows, the buffer they were
+        generated into) of its first round when a batched round has run it already: the round
+        is then accounted and read as if it had run here."""
+        st = self.stats
+        b, key, keccak_reads, base_schema = s.b, s.key, s.keccak_reads, s.base_schema
+        columns, widths, schema, root_nodes, ts, group_cols, defs, root_ends = s.host
+        col_index, parent, parent_len = s.col_index, s.parent, s.parent_len
+        guide, ct, t1 = s.guide, s.ct, s.t1
         t_c = time.perf_counter()
         round_guide = guide  # the incremental round's own guide replaces it (closed below)
         inc_guide = None
@@ -970,7 +1186,9 @@ class Sieve:
         st.add("compile_flatten", ft)
         st.add("compile_native", nt)
         try:
-            assign = self._buffer(len(columns))
+            # (after a batched first round the sieve's own buffer is made when a later round or
+            # the repair step needs it)
+            assign = self._buffer(len(columns)) if first is None else None
             values: Dict[str, int] = {}
             solved = [False] * len(group_cols)
             first_index = None
@@ -1018,21 +1236,26 @@ class Sieve:
                         st.extra["inc_rounds"] = st.extra.get("inc_rounds", 0) + 1
                         self.last_rounds["incremental"] = 1
                 self.last_rounds["rounds"] = rnd + 1
-                base = (self.stats.queries << 24) + offset
+                base = (s.qno << 24) + offset
                 offset += n
                 last_n = n
                 tb = time.perf_counter()
                 # a later round runs only the tapes from the first to the last unsolved group
                 g0 = solved.index(False)
                 g1 = len(solved) - solved[::-1].index(False)
-                # generator, run, and the first witnesses with their rows' columns in one call and
-                # one copy back (mh_query_round)
-                fh, _, wrows = native.query_round(self.ctx, ct, assign, round_guide, self.seed,
-                                                  base, n, len(columns), tape_first=g0,
-                                                  tape_count=g1 - g0,
-                                                  mode=native.MODE_FIRST_HIT)
-                tr = time.perf_counter()
-                st.add("run", tr - tb)
+                if rnd == 0 and first is not None:
+                    fh, wrows = first[0], first[1]  # run by solve_many's batched round
+                else:
+                    if assign is None:
+                        assign = self._buffer(len(columns))
+                    # generator, run, and the first witnesses with their rows' columns in one call
+                    # and one copy back (mh_query_round)
+                    fh, _, wrows = native.query_round(self.ctx, ct, assign, round_guide, self.seed,
+                                                      base, n, len(columns), tape_first=g0,
+                                                      tape_count=g1 - g0,
+                                                      mode=native.MODE_FIRST_HIT)
+                    tr = time.perf_counter()
+                    st.add("run", tr - tb)
                 self.stats.rounds += 1
                 self.stats.rows += n
                 for i, hit in enumerate(fh.tolist()):
@@ -1061,7 +1284,15 @@ class Sieve:
                     break
             if (self.repair_rounds > 0 and last_n and not all(solved)
                     and time.perf_counter() - t0 <= budget):
-                base = (self.stats.queries << 24) + offset
+                if assign is None:
+                    # repair straight after a batched first round: its rows regenerated into the
+                    # buffer repair reads (and writes children into), the one sequential solve
+                    # leaves them in -- one deterministic launch on a rare path
+                    assign = self._buffer(len(columns))
+                    assign.generate_guided(self.seed, guide.arrays(), global_base=s.qno << 24,
+                                           first=0, count=last_n)
+                    st.extra["repair_regenerated"] = st.extra.get("repair_regenerated", 0) + 1
+                base = (s.qno << 24) + offset
                 hit = self._repair(root_nodes, ts, ct, guide, assign, last_n, columns, group_cols,
                                    solved, values, base, budget, t0)
                 if hit is not None:
@@ -1085,7 +1316,8 @@ class Sieve:
             guide.close()
             if inc_guide is not None:
                 inc_guide.close()
-            self.stats.device_s += time.perf_counter() - t1
+            # (a batched query's stage ended before the other queries' stages and the batch)
+            self.stats.device_s += time.perf_counter() - (t1 if first is None else t_c)
 
     def _repair(self, root_nodes, ts, ct, guide, assign, n_rows, columns, group_cols, solved,
                 values, base, budget, t0):

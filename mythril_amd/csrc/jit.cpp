@@ -277,6 +277,8 @@ private:
     void op_shl(int d, const Val& A, uint32_t s);
     void op_vshift(int d, const Val& A, const Val& B, uint8_t op);
     void op_mul(int d, const Val& A, const Val& B);
+    void op_mul_open(int d, const Val& A, const Val& B);
+    static uint32_t open_mul_slack(const Val& A, const Val& B);
     void op_div(int d, int a, int b, int cidx, uint32_t kind, int cur);
     void div_undecided(Opnd decided, int cur);
     void div_short_dividend(const Val& A, const Val& B, uint32_t kind, int nx, uint32_t dm, int cur,
@@ -304,7 +306,7 @@ public:
 private:
     std::vector<Stage> stages_;
     std::vector<Slack> slack_;               // of the slice values (layer 3), by vreg
-    std::vector<uint8_t> slack_ok_;          // slice add/sub that may leave the carry-in open
+    std::vector<uint8_t> slack_ok_;          // slice add/sub/mul that may leave the carry-in open
     bool in_slice_ = false;
     void plan_stages();
     void emit_staged(const Stage& sg);
@@ -1052,7 +1054,106 @@ void Emitter::op_vshift(int d, const Val& A, const Val& B, uint8_t op) {
 // x * y mod 2^256, product scanning over the demanded columns: column k accumulates its terms
 // with v_mad_u64_u32 into a 64-bit pair; carries out of the pair (only where the column can
 // exceed 2^64) are counted into the next column's high word.
+//
+// An open product (emit_staged, layer 4: a slice that asks for the top limb alone, of a consumer
+// that tolerates slack) runs columns 6 and 7 only.  With C_k the sum of column k's terms,
+//   T = (C_7 + floor(C_6 / 2^32)) mod 2^32
+// and the true limb 7 is (C_7 + floor((C_6 + c) / 2^32)) mod 2^32, c the carry of columns 0..5
+// into column 6: T + e, e = floor((C_6 mod 2^32 + c) / 2^32) in [0, open_mul_slack()].  C_6 may
+// wrap at 64 bits: what wraps weighs 2^256.  Column 6 accumulates without carry counting, column
+// 7 onto its high word (one move: 64-bit operands are even-aligned pairs); only the low word of
+// column 7's accumulator is read, so the high word of its carry-in pair is never written.
+uint32_t Emitter::open_mul_slack(const Val& A, const Val& B) {
+    // the largest e: carries by op_mul's bound arithmetic, cm_0 = 0, cm_(k+1) =
+    // floor((cm_k + sum of column k's largest terms) / 2^32) -- a limb is its constant or at most
+    // 2^32 - 1, a term with a known-zero limb is absent -- and C_6 mod 2^32 <= min(2^32 - 1,
+    // column 6's largest sum): hi = floor((min(2^32 - 1, max C_6) + cm_6) / 2^32).  Variable
+    // operands give cm_6 = 6 * 2^32 - 7 and hi = 6; a 32-bit constant factor gives hi <= 1, the
+    // factor 1 gives 0.
+    typedef unsigned __int128 u128;
+    const u128 M32 = 0xFFFFFFFFull;
+    auto maxv = [&](const Limb& l) -> u128 { return l.is_c() ? (u128)l.v : M32; };
+    u128 cm = 0, c6 = 0;
+    for (int k = 0; k <= 6; ++k) {
+        u128 col = 0;
+        for (int i = 0; i <= k; ++i) {
+            const Limb x = A.l[i], y = B.l[k - i];
+            if (x.is_c(0) || y.is_c(0)) continue;
+            col += maxv(x) * maxv(y);
+        }
+        if (k == 6) c6 = std::min(col, M32);
+        else cm = (cm + col) >> 32;
+    }
+    return (uint32_t)((c6 + cm) >> 32);
+}
+
+void Emitter::op_mul_open(int d, const Val& A, const Val& B) {
+    Val& R = out(d);
+    // terms of two constant limbs fold into kc: column 6's in full, column 7's on its high word
+    uint64_t kc = 0;
+    std::vector<std::pair<int, int>> terms[2];
+    for (int k = 6; k <= 7; ++k)
+        for (int i = 0; i <= k; ++i) {
+            const Limb x = A.l[i], y = B.l[k - i];
+            if (x.is_c(0) || y.is_c(0)) continue;
+            if (x.k == L_UNDEF || y.k == L_UNDEF) fail("internal: mul over an undemanded limb");
+            if (x.is_c() && y.is_c()) {
+                const uint64_t p = (uint64_t)x.v * y.v;
+                kc += k == 6 ? p : p << 32;
+                continue;
+            }
+            terms[k - 6].push_back({i, k - i});
+        }
+    auto mad = [&](uint32_t acc, std::pair<int, int> t, Opnd s2) {
+        Limb x = A.l[t.first], y = B.l[t.second];
+        if (x.is_c()) std::swap(x, y);
+        const Opnd s0 = y.is_c() ? staged(y.v) : V(y.v);
+        emit(M_V_MAD_U64_U32, {V(acc, 2), S(S_DIV_DUMMY, 2), s0, V(x.v), s2});
+    };
+    uint32_t acc = ~0u;
+    if (!terms[0].empty()) {
+        acc = valloc_pair();
+        Opnd s2 = IMM(0);
+        if (kc) {
+            emit(M_V_MOV, {V(acc), IMM((uint32_t)kc)});
+            emit(M_V_MOV, {V(acc + 1), IMM((uint32_t)(kc >> 32))});
+            s2 = V(acc, 2);
+        }
+        for (auto t : terms[0]) {
+            mad(acc, t, s2);
+            s2 = V(acc, 2);
+        }
+    }
+    if (terms[1].empty()) {  // T is the high word of column 6
+        if (acc == ~0u) {
+            R.l[7] = Limb::C((uint32_t)(kc >> 32));
+        } else {
+            R.l[7] = Limb::R(acc + 1);
+            vrelease(acc);
+        }
+        return;
+    }
+    const uint32_t np = valloc_pair();
+    Opnd s2 = V(np, 2);
+    if (acc != ~0u) {
+        emit(M_V_MOV, {V(np), V(acc + 1)});
+        vrelease(acc);
+        vrelease(acc + 1);
+    } else if ((uint32_t)(kc >> 32)) {
+        emit(M_V_MOV, {V(np), IMM((uint32_t)(kc >> 32))});
+    } else {
+        s2 = IMM(0);
+    }
+    for (auto t : terms[1]) {
+        mad(np, t, s2);
+        s2 = V(np, 2);
+    }
+    R.l[7] = Limb::R(np);
+    vrelease(np + 1);
+}
+
 void Emitter::op_mul(int d, const Val& A, const Val& B) {
+    if (in_slice_ && slack_ok_[d]) return op_mul_open(d, A, B);
     const int top = top_bit(dem_[d]);
     Val& R = out(d);
     if (top < 0) return;
@@ -2134,6 +2235,19 @@ void Emitter::emit_staged(const Stage& sg) {
             slack_ok_[v.d] = 1;
             ask(v.a, 0x80u, false);
             if (v.cidx < 0) ask(v.b, 0x80u, false);
+        } else if (stage_ >= 4 && open_carry && !ex && dd == 0x80u && v.op == D_MUL_R) {
+            // an open product (op_mul_open): columns 6 and 7 of exact operands; by a constant
+            // factor, the limbs that meet one of its non-zero limbs there
+            slack_ok_[v.d] = 1;
+            uint32_t ma = 0xFFu;
+            if (v.cidx >= 0) {
+                ma = 0;
+                for (int k = 6; k <= 7; ++k)
+                    for (int i = 0; i <= k; ++i)
+                        if (pool_[8ull * (uint32_t)v.cidx + (uint32_t)(k - i)]) ma |= 1u << i;
+            }
+            ask(v.a, ma, true);
+            if (v.cidx < 0) ask(v.b, 0xFFu, true);
         } else if (v.op == D_NOP) {
             ask(v.a, dd, ex);
         } else if (v.op == D_ITE) {
@@ -2162,7 +2276,9 @@ void Emitter::emit_staged(const Stage& sg) {
         const Slack a = v.a >= 0 ? slack_[v.a] : Slack();
         const Slack b = v.cidx < 0 && v.b >= 0 ? slack_[v.b] : Slack();
         Slack r;
-        if (slack_ok_[v.d]) {
+        if (slack_ok_[v.d] && v.op == D_MUL_R) {
+            r.hi = open_mul_slack(val(v.a), v.cidx >= 0 ? const_val(v.cidx) : val(v.b));
+        } else if (slack_ok_[v.d]) {
             if (v.op == D_ADD_R) { r.lo = a.lo + b.lo; r.hi = a.hi + b.hi + 1; }
             else if (v.op == D_SUB_R) { r.lo = a.lo + b.hi + 1; r.hi = a.hi + b.lo; }
             else { r.lo = b.lo + a.hi + 1; r.hi = b.hi + a.lo; }  // y - a
@@ -3932,10 +4048,11 @@ uint32_t coalesce_div_moves(std::vector<MI>& code) {
 static std::atomic<uint64_t> g_sc_fallbacks{0};
 
 // Staged conjuncts (emit_staged): MH_JIT_STAGE = 0 off, 1 == conjuncts, 2 + ordered compares from
-// exact top limbs, 3 + add / sub with the carry-in left open.
+// exact top limbs, 3 + add / sub with the carry-in left open, 4 + products from their two top
+// columns.
 static int stage_level() {
     const char* e = std::getenv("MH_JIT_STAGE");  // read per tape: tests switch it in-process
-    return e ? std::min(3, std::max(0, atoi(e))) : 3;
+    return e ? std::min(4, std::max(0, atoi(e))) : 4;
 }
 
 // Inline division fast paths (Emitter::op_div): MH_JIT_DIV = 0 off, 1 dividends known shorter
@@ -3993,6 +4110,15 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
                     e3.div_ = dlevel;
                     e3.stage_skip_ = &skip;
                     tc = e3.run();
+                }
+                if (tc.ok && level >= 4 && tc.max_vgpr > Options().max_vgpr) {
+                    // over the default budget (a retry at a larger one): open products stage more
+                    // conjuncts, and a slice's temporaries are all live at its decision -- not at
+                    // the price of a register granule, which is occupancy there
+                    Options o3 = opt;
+                    o3.stage = 3;
+                    TapeCode t3 = emit_tape_body(st, pool, n_vars, o3);
+                    if (t3.ok && (t3.max_vgpr + 7) / 8 < (tc.max_vgpr + 7) / 8) return t3;
                 }
                 if (tc.ok) return tc;  // else (register pressure of the slices): unstaged
             }

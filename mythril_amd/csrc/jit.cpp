@@ -16,6 +16,7 @@
 // first moved into a VGPR (v_mov, a 2-cycle instruction) or staged in an SGPR (s_mov).
 #include "jit.h"
 
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -24,6 +25,7 @@
 #include <atomic>
 #include <climits>
 #include <cstdlib>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -40,6 +42,46 @@ struct Fail {
 };
 
 [[noreturn]] void fail(const std::string& w) { throw Fail{w}; }
+
+// Bits of the f64 nearest to 2^(32 max(ny - 3, 0)) / y (round to nearest even) for a constant
+// divisor y != 0 of ny limbs: the reciprocal in the units of the variants' remainder windows
+// (div_routine).  q = floor(2^n / y) by shift and subtract with n = bitlen(y) + 53, so
+// 2^53 <= q <= 2^54: 54 significant bits, one more than f64 keeps, plus the remainder as sticky.
+uint64_t div_recip_bits(const uint32_t* y, int ny) {
+    int len = 0;
+    for (int k = 0; k < 8; ++k)
+        if (y[k]) len = 32 * k + 32 - __builtin_clz(y[k]);
+    uint32_t rem[9] = {0};
+    uint64_t q = 0;
+    for (int i = 0; i <= len + 53; ++i) {  // the numerator's bits: a one, then n zeros
+        for (int k = 8; k > 0; --k) rem[k] = rem[k] << 1 | rem[k - 1] >> 31;
+        rem[0] = rem[0] << 1 | (i == 0 ? 1u : 0u);
+        bool ge = rem[8] != 0;
+        if (!ge) {
+            ge = true;
+            for (int k = 7; k >= 0; --k)
+                if (rem[k] != y[k]) { ge = rem[k] > y[k]; break; }
+        }
+        q <<= 1;
+        if (ge) {
+            uint64_t borrow = 0;
+            for (int k = 0; k < 9; ++k) {
+                const uint64_t t = (uint64_t)rem[k] - (k < 8 ? y[k] : 0u) - borrow;
+                rem[k] = (uint32_t)t;
+                borrow = (t >> 32) & 1;
+            }
+            q |= 1;
+        }
+    }
+    bool sticky = false;
+    for (int k = 0; k < 9; ++k) sticky = sticky || rem[k];
+    uint64_t m = q >> 1;
+    if ((q & 1) && (sticky || (m & 1))) ++m;
+    const double r = ldexp((double)m, -(len + 52) + 32 * std::max(ny - 3, 0));
+    uint64_t b;
+    memcpy(&b, &r, 8);
+    return b;
+}
 
 enum LK : uint8_t { L_UNDEF, L_CONST, L_VGPR };
 struct Limb {
@@ -101,6 +143,7 @@ private:
     uint32_t n_valu_cold_ = 0;
     int cold_ = 0;
     bool calls_div_ = false;
+    bool calls_divw_ = false;  // some site calls a width-specialised variant (op_div)
     bool uses_lds_ = false;
     bool calls_kec_ = false;
     int cur_op_ = -1;  // SSA op being emitted (diagnostic attribution)
@@ -108,6 +151,7 @@ private:
 public:
     static uint64_t op_valu[256], op_wide[256], op_count[256];
     int div_ = 0;  // inline division fast paths (op_div): the MH_JIT_DIV level, 0 = off
+    bool divw_ = false;  // width-specialised division variants (MH_JIT_STAGE >= 5, MH_JIT_DIV > 0)
 private:
 
     // ---- emission
@@ -1521,14 +1565,58 @@ void Emitter::op_div(int d, int a, int b, int cidx, uint32_t kind, int cur) {
         load_abs(R_DY, R_SY, B);
         load_abs(R_DR, R_SX, A);
     }
-    emit(M_S_MOV_B32, {S(S_DIV_KIND), IMM(kind)});
+    // Width-specialised variants: a called site whose divisor is known to
+    // fit ny <= 7 limbs enters the subroutine at the variant for ny, at the start digit
+    // j0 = nx - ny that the widths bound (x < 2^(32 nx) <= y 2^(32 (j0 + 1)) wherever y's limb
+    // ny - 1 is nonzero).  S_DIV_KIND = kind | (64 const + 8 ny + j0) << 3 selects it, the plain
+    // kind travels in S_DIV_DUMMY's low half (the variants keep it; they restore S_DIV_KIND from
+    // it for the shared tail and for the legacy code a short divisor falls back to), and a
+    // constant divisor brings its reciprocal, rounded on the host, in S_DIV_F64K.  Both operands
+    // are loaded whole as before: the tail and the fallback read every limb.
+    int wny = 0;
+    bool wconst = false;
+    uint32_t yc[8] = {0};
+    if (divw_ && path == 0) {
+        wconst = true;
+        for (int k = 0; k < 8; ++k) wconst = wconst && B.l[k].is_c();
+        if (wconst) {  // |y|, as load_abs forms it for the signed kinds
+            const bool neg = kind >= 2 && (B.l[7].v >> 31);
+            uint64_t carry = neg ? 1 : 0;
+            for (int k = 0; k < 8; ++k) {
+                const uint64_t t = (uint64_t)(neg ? ~B.l[k].v : B.l[k].v) + carry;
+                yc[k] = (uint32_t)t;
+                carry = t >> 32;
+            }
+            wny = 8;
+            while (wny > 0 && !yc[wny - 1]) --wny;
+        } else {
+            wny = ny;
+        }
+        if (wny < 1 || wny > 7 || nx < wny) wny = 0;
+    }
+    if (wny) {
+        const int j0 = nx - wny;
+        calls_divw_ = true;
+        emit(M_S_MOV_B32, {S(S_DIV_KIND), IMM(kind | (uint32_t)((wconst ? 64 : 0) + 8 * wny + j0) << 3)});
+        emit(M_S_MOV_B32, {S(S_DIV_DUMMY), IMM(kind)});
+        if (wconst) {
+            const uint64_t rb = div_recip_bits(yc, wny);
+            emit(M_S_MOV_B32, {S(S_DIV_F64K), IMM((uint32_t)rb)});
+            emit(M_S_MOV_B32, {S(S_DIV_F64K + 1), IMM((uint32_t)(rb >> 32))});
+        }
+    } else {
+        emit(M_S_MOV_B32, {S(S_DIV_KIND), IMM(kind)});
+    }
     emit(M_CALL_DIV, {IMM((uint32_t)code_.size())});
     if (path) {
         --cold_;
         emit(M_LABEL, {LBL(l_join)});
     }
     // a remainder of a short dividend is as short on both sides (|r| <= |x|, and x % 0 = x)
-    const int nr = path == 1 && (kind & 1) ? nx : 8;
+    int nr = path == 1 && (kind & 1) ? nx : 8;
+    // a constant divisor is nonzero: q = x / y < 2^(32 (nx - ny + 1)) and r < y < 2^(32 ny) (the
+    // unsigned kinds; a variable y = 0 gives q = 2^256 - 1 and r = x, so nothing is known there)
+    if (wny && wconst && kind < 2) nr = kind == 1 ? wny : nx - wny + 1;
     Val& R = out(d);
     for (int k = 0; k < 8; ++k)
         if ((dm >> k) & 1) R.l[k] = k < nr ? Limb::R(rbase + k) : Limb::C(0);
@@ -2556,6 +2644,7 @@ TapeCode Emitter::run() {
     tc.code.swap(code_);
     tc.max_vgpr = vhigh_;
     tc.calls_div = calls_div_;
+    tc.calls_divw = calls_divw_;
     tc.uses_lds = uses_lds_;
     tc.calls_kec = calls_kec_;
     tc.n_valu = n_valu_;
@@ -2716,6 +2805,43 @@ std::vector<MI> div_routine() {
     };
     auto Rl = [](int k) { return V(R_DR + k); };
     auto Yl = [](int k) { return V(R_DY + k); };
+    // ---- width-specialised variants (round 10): the dispatch.  A variant site (op_div) writes
+    // S_DIV_KIND = kind | e << 3 with e = 64 const + 8 ny + j0 >= 8; legacy sites write 0..4 and
+    // fall through to L_UNS.  Labels from 128 up mark what build_module leaves out of a module
+    // none of whose tapes has a variant site: [L_WHEAD, L_UNS) and [L_WSEC, end).
+    // KEEP = the plain kind (the site puts it in S_DIV_DUMMY's low half; the variants' products
+    // take S_DIV_MSK for their unused carry-out instead).
+    const Opnd KEEP = S(S_DIV_DUMMY);
+    enum : uint32_t { L_WHEAD = 128, L_WSEC, L_WCONST, L_WVAR = 136 /* + ny */, L_WCON = 144 /* + ny */,
+                      L_WOK = 152 /* + ny */, L_WZQ = 160 /* + 2 (8 c + ny) */,
+                      L_WSTEP = 256 /* + 16 ny + j */, L_WNONEG = 384, L_WNOGE = 512,
+                      L_WTREE = 640 };
+    L(L_WHEAD);
+    E(M_S_CMP_LT_U32, {KIND, IMM(64)});
+    E(M_S_CBRANCH_SCC1, {LBL(L_UNS)});
+    {
+        uint32_t tree = L_WTREE;
+        // binary search over ny in [lo, hi] of the variants of one constness (e's bit 6)
+        std::function<void(int, int, uint32_t, uint32_t)> pick = [&](int lo, int hi, uint32_t c,
+                                                                      uint32_t base) {
+            if (lo == hi) {
+                E(M_S_BRANCH, {LBL(base + (uint32_t)lo)});
+                return;
+            }
+            const int mid = (lo + hi + 1) / 2;
+            const uint32_t l = tree++;
+            E(M_S_CMP_LT_U32, {KIND, IMM((64 * c + 8 * (uint32_t)mid) << 3)});
+            E(M_S_CBRANCH_SCC0, {LBL(l)});
+            pick(lo, mid - 1, c, base);
+            L(l);
+            pick(mid, hi, c, base);
+        };
+        E(M_S_CMP_LT_U32, {KIND, IMM(64u << 3)});
+        E(M_S_CBRANCH_SCC0, {LBL(L_WCONST)});
+        pick(1, 7, 0, L_WVAR);
+        L(L_WCONST);
+        pick(1, 7, 1, L_WCON);
+    }
     // signed kinds arrive as |x|, |y| with the sign masks in SX, SY (the call site forms them)
     L(L_UNS);
     // the quotient registers start at 0 for the kinds that return the quotient (the digit steps
@@ -3037,6 +3163,214 @@ std::vector<MI> div_routine() {
     }
     L(L_WB);
     E(M_RET, {});
+    // ---- width-specialised variants (round 10) -----------------------------------
+    // Variant ny (1..7) serves divisors below 2^(32 ny), entered at digit j0 = nx - ny (the
+    // site's widths), variable or constant.  All of them end in the shared tail at L_DONE with
+    // S_DIV_KIND restored and YNZ set.
+    L(L_WSEC);
+    const Opnd WD = MSK;  // carry-out of the products: unused, and MSK is free while they run
+    auto leave = [&](uint32_t to) {
+        E(M_S_MOV_B32, {KIND, KEEP});
+        E(M_S_BRANCH, {LBL(to)});
+    };
+    // the quotient registers start at 0 where a quotient kind reads limbs the digits do not
+    // write: udiv and sdiv of a variable divisor, sdiv of a constant one (its tail negates all
+    // eight; udiv's limbs above j0 are declared zero at the site and never read)
+    auto zero_q = [&](bool isconst, int ny) {
+        const uint32_t l = L_WZQ + 2 * (uint32_t)(8 * isconst + ny);
+        if (!isconst) {
+            E(M_S_CMP_EQ_U32, {KEEP, IMM(0)});
+            E(M_S_CBRANCH_SCC1, {LBL(l)});
+        }
+        E(M_S_CMP_EQ_U32, {KEEP, IMM(2)});
+        E(M_S_CBRANCH_SCC0, {LBL(l + 1)});
+        L(l);
+        for (int k = 0; k < 8; ++k) E(M_V_MOV, {Xr(k), IMM(0)});
+        L(l + 1);
+    };
+    // enter the digit the site's widths name: e's low three bits
+    auto enter = [&](bool isconst, int ny, int jmax) {
+        const uint32_t base = (uint32_t)(64 * isconst + 8 * ny) << 3;
+        if (jmax > 0) {  // the full-width dividend first
+            E(M_S_CMP_LT_U32, {KIND, IMM(base + 8 * (uint32_t)jmax)});
+            E(M_S_CBRANCH_SCC0, {LBL(L_WSTEP + 16 * (uint32_t)ny + (uint32_t)jmax)});
+        }
+        for (int j = jmax - 1; j > 0; --j) {
+            E(M_S_CMP_LT_U32, {KIND, IMM(base + 8 * (uint32_t)j)});
+            E(M_S_CBRANCH_SCC0, {LBL(L_WSTEP + 16 * (uint32_t)ny + (uint32_t)j)});
+        }
+        E(M_S_BRANCH, {LBL(L_WSTEP + 16 * (uint32_t)ny)});
+    };
+    auto const_recip = [&]() {  // the site's host-rounded reciprocal, before K64 is reused
+        E(M_V_MOV, {V(R_FY), K64LO});
+        E(M_V_MOV, {V(R_FY + 1), K64HI});
+        E(M_S_MOV_B64, {YNZ, IMM(0xFFFFFFFFu)});
+    };
+    // -- ny = 1: L_NARROW entered knowing every lane narrow, so without the OR over y's limbs
+    // and the x < y borrow chain (such a lane's digits are simply 0), from digit nx - 1 down.
+    // Each digit's remainder moves to C and its register is zeroed on the way (lanes with y = 0
+    // keep x there), instead of a pass over R[1..7] at the end.
+    L(L_WVAR + 1);
+    zero_q(false, 1);
+    E(M_V_CMP_NE, {YNZ, IMM(0), Yr(0)}, true);
+    E(M_V_CVT_F64_U32, {FY, Yr(0)});
+    recip();
+    E(M_V_CNDMASK, {V(R_FY), IMM(0), V(R_FY), YNZ}, true);
+    E(M_V_CNDMASK, {V(R_FY + 1), IMM(0), V(R_FY + 1), YNZ}, true);
+    E(M_V_MOV, {C, IMM(0)});
+    enter(false, 1, 7);
+    L(L_WCON + 1);
+    zero_q(true, 1);
+    const_recip();
+    E(M_V_MOV, {C, IMM(0)});
+    enter(true, 1, 7);
+    for (int k = 7; k >= 0; --k) {
+        const uint32_t id = 16 + (uint32_t)k;
+        L(L_WSTEP + id);
+        E(M_S_MOV_B32, {K64LO, IMM(0)});
+        E(M_S_MOV_B32, {K64HI, IMM(0x41f00000u)});  // 2^32
+        E(M_V_CVT_F64_U32, {FR, C});
+        E(M_V_CVT_F64_U32, {FT, Rr(k)});
+        E(M_V_FMA_F64, {FR, FR, K64, FT});      // r 2^32 + R[k]
+        E(M_V_MUL_F64, {FC, FR, FY});
+        E(M_S_MOV_B32, {K64LO, IMM(0xffe00000u)});
+        E(M_S_MOV_B32, {K64HI, IMM(0x41efffffu)});
+        E(M_V_MIN_F64, {FC, FC, K64});
+        E(M_V_CVT_U32_F64, {Xr(k), FC});          // digit estimate, the digit or off by one
+        E(M_V_MAD_U64_U32, {MAD, WD, Xr(k), Yr(0), IMM(0)});
+        E(M_V_SUB_CO, {Rr(k), VCC(), Rr(k), V(R_MAD)});
+        E(M_V_SUBB_CO, {T1, VCC(), C, V(R_MAD + 1), VCC()});    // borrow: estimate one too high
+        E(M_S_MOV_B64, {TM, VCC()});
+        E(M_S_CMP_EQ_U64, {TM, IMM(0)});
+        E(M_S_CBRANCH_SCC1, {LBL(L_WNONEG + id)});
+        E(M_V_CNDMASK, {T1, IMM(0), Yr(0), TM}, true);
+        E(M_V_CNDMASK, {C, IMM(0), IMM(1), TM}, true);
+        E(M_V_ADD_U32, {Rr(k), Rr(k), T1});
+        E(M_V_SUB_U32, {Xr(k), Xr(k), C});
+        L(L_WNONEG + id);
+        E(M_V_CMP_GE, {VCC(), Rr(k), Yr(0)});              // one too low: r >= d
+        E(M_S_AND_B64, {TM, VCC(), YNZ});
+        E(M_S_CMP_EQ_U64, {TM, IMM(0)});
+        E(M_S_CBRANCH_SCC1, {LBL(L_WNOGE + id)});
+        E(M_V_CNDMASK, {T1, IMM(0), Yr(0), TM}, true);
+        E(M_V_CNDMASK, {C, IMM(0), IMM(1), TM}, true);
+        E(M_V_SUB_U32, {Rr(k), Rr(k), T1});
+        E(M_V_ADD_U32, {Xr(k), Xr(k), C});
+        L(L_WNOGE + id);
+        if (k) {
+            E(M_V_MOV, {C, Rr(k)});                              // the next digit's r
+            E(M_V_CNDMASK, {Rr(k), Rr(k), IMM(0), YNZ}, true);  // and R[k] = 0 where y != 0
+        }
+    }
+    leave(L_DONE);
+    // -- 2 <= ny <= 7: L_TOP3 generalised from y >= 2^224 to y >= 2^(32 (ny - 1)).  Guard
+    // (variable y): limb ny - 1 nonzero in every lane; one lane with a shorter divisor (y = 0
+    // too) sends the wave to the legacy code, which has both operands whole.  Past it YNZ is all
+    // ones and no lane needs masking: a lane with x < y estimates digits of 0, or of 1 that the
+    // add-back takes away.
+    //   Invariant: before step j, R < y 2^(32 (j + 1)) -- at j0 because x < 2^(32 nx) =
+    // 2^(32 (j0 + ny)) <= y 2^(32 (j0 + 1)), afterwards because a step leaves R < y 2^(32 j).  So
+    // the digit c = floor(R / (y 2^(32 j))) < 2^32, and R < 2^(32 (j + ny + 1)): limb j + ny can
+    // be nonzero, nothing above it.
+    //   Estimate: w = W / 2^(32 max(ny - 3, 0)) of y's top three limbs (two for ny = 2, exact)
+    // and Rw of R's limbs j + ny .. j + ny - 3 in the same units times 2^(32 j); est = Rw / w.
+    // Cutting y below its top 96 bits and R below its top 97..128 moves est by < 2^-63 relative.
+    // Roundings, u = 2^-53 each: Rw three fma, w two, the reciprocal 2 u after two Newton steps
+    // (as L_TOP3 relies on; the host's is u), the product one: 8 u = 2^-50 relative, so
+    // |est - R / (y 2^(32 j))| < 2^32 2^-50 = 2^-18 < 2^-17.  Hence c = trunc(est) is the digit,
+    // one above it (R goes negative: the add-back) or one below it, and then fract(est) >
+    // 1 - 2^-17: only waves with such a lane run the "R >= y" test.  An estimate at or above
+    // 2^32 means the digit 2^32 - 1: the clamp, whose fraction is 0.
+    for (int ny = 2; ny <= 7; ++ny) {
+        const int jmax = 8 - ny, wl = std::min(ny, 3);
+        L(L_WVAR + (uint32_t)ny);
+        E(M_V_CMP_NE, {VCC(), IMM(0), Yr(ny - 1)});
+        E(M_S_CMP_EQ_U64, {VCC(), IMM(0xFFFFFFFFu)});
+        E(M_S_CBRANCH_SCC1, {LBL(L_WOK + (uint32_t)ny)});
+        leave(L_UNS);
+        L(L_WOK + (uint32_t)ny);
+        zero_q(false, ny);
+        E(M_S_MOV_B32, {K64LO, IMM(0)});
+        E(M_S_MOV_B32, {K64HI, IMM(0x41f00000u)});  // 2^32
+        E(M_V_CVT_F64_U32, {FY, Yr(ny - 1)});
+        for (int k = ny - 2; k >= ny - wl; --k) {
+            E(M_V_CVT_F64_U32, {FT, Yr(k)});
+            E(M_V_FMA_F64, {FY, FY, K64, FT});
+        }
+        recip();
+        E(M_S_MOV_B64, {YNZ, IMM(0xFFFFFFFFu)});
+        enter(false, ny, jmax);
+        L(L_WCON + (uint32_t)ny);
+        zero_q(true, ny);
+        const_recip();
+        enter(true, ny, jmax);
+        for (int j = jmax; j >= 0; --j) {
+            const uint32_t id = 16 * (uint32_t)ny + (uint32_t)j;
+            const int top = j + ny;  // the borrow limb; limb 8 does not exist (first step only)
+            L(L_WSTEP + id);
+            E(M_S_MOV_B32, {K64LO, IMM(0)});
+            E(M_S_MOV_B32, {K64HI, IMM(0x41f00000u)});  // 2^32
+            const int hi = top <= 7 ? top : top - 1;
+            E(M_V_CVT_F64_U32, {FR, Rr(hi)});
+            for (int k = hi - 1; k >= top - wl; --k) {
+                E(M_V_CVT_F64_U32, {FT, Rr(k)});
+                E(M_V_FMA_F64, {FR, FR, K64, FT});
+            }
+            E(M_V_MUL_F64, {FC, FR, FY});
+            E(M_S_MOV_B32, {K64LO, IMM(0xffe00000u)});
+            E(M_S_MOV_B32, {K64HI, IMM(0x41efffffu)});  // 2^32 - 1
+            E(M_V_MIN_F64, {FC, FC, K64});
+            E(M_V_CVT_U32_F64, {C, FC});
+            E(M_V_FRACT_F64, {FT, FC});
+            E(M_S_MOV_B32, {K64LO, IMM(0)});
+            E(M_S_MOV_B32, {K64HI, IMM(0x3feffff0u)});  // 1 - 2^-17
+            E(M_V_CMP_LE_F64, {VCC(), K64, FT});
+            E(M_S_MOV_B64, {TM, VCC()});
+            // R[j .. j + ny] -= c y
+            for (int k = 0; k < ny; ++k) {
+                E(M_V_MAD_U64_U32, {MAD, WD, C, Yr(k), k ? CARRY : IMM(0)});
+                if (k == 0) E(M_V_MOV, {V(R_CARRY + 1), IMM(0)});
+                E(M_V_MOV, {V(R_CARRY), V(R_MAD + 1)});
+                if (k == 0) E(M_V_SUB_CO, {Rr(j), VCC(), Rr(j), V(R_MAD)});
+                else E(M_V_SUBB_CO, {Rr(j + k), VCC(), Rr(j + k), V(R_MAD), VCC()});
+            }
+            if (top <= 7) E(M_V_SUBB_CO, {Rr(top), VCC(), Rr(top), V(R_CARRY), VCC()});
+            else E(M_V_SUBB_CO, {T1, VCC(), IMM(0), V(R_CARRY), VCC()});
+            // negative: add y << 32j back, c - 1
+            E(M_S_MOV_B64, {MSK, VCC()});
+            E(M_S_CMP_EQ_U64, {MSK, IMM(0)});
+            E(M_S_CBRANCH_SCC1, {LBL(L_WNONEG + id)});
+            for (int k = 0; k < ny; ++k) {
+                E(M_V_CNDMASK, {T1, IMM(0), Yr(k), MSK}, true);
+                if (k == 0) E(M_V_ADD_CO, {Rr(j), VCC(), Rr(j), T1});
+                else E(M_V_ADDC_CO, {Rr(j + k), VCC(), Rr(j + k), T1, VCC()});
+            }
+            if (top <= 7) E(M_V_ADDC_CO, {Rr(top), VCC(), IMM(0), Rr(top), VCC()});
+            E(M_V_CNDMASK, {T1, IMM(0), IMM(1), MSK}, true);
+            E(M_V_SUB_U32, {C, C, T1});
+            L(L_WNONEG + id);
+            // R >= y << 32j: subtract once more, c + 1
+            E(M_S_CMP_EQ_U64, {TM, IMM(0)});
+            E(M_S_CBRANCH_SCC1, {LBL(L_WNOGE + id)});
+            E(M_V_SUB_CO, {T1, VCC(), Rr(j), Yr(0)});
+            for (int k = 1; k < ny; ++k) E(M_V_SUBB_CO, {T1, VCC(), Rr(j + k), Yr(k), VCC()});
+            if (top <= 7) E(M_V_SUBBREV_CO, {T1, VCC(), IMM(0), Rr(top), VCC()});
+            E(M_S_ANDN2_B64, {MSK, YNZ, VCC()});
+            E(M_S_CMP_EQ_U64, {MSK, IMM(0)});
+            E(M_S_CBRANCH_SCC1, {LBL(L_WNOGE + id)});
+            for (int k = 0; k < ny; ++k) {
+                E(M_V_CNDMASK, {T1, IMM(0), Yr(k), MSK}, true);
+                if (k == 0) E(M_V_SUB_CO, {Rr(j), VCC(), Rr(j), T1});
+                else E(M_V_SUBB_CO, {Rr(j + k), VCC(), Rr(j + k), T1, VCC()});
+            }
+            if (top <= 7) E(M_V_SUBBREV_CO, {Rr(top), VCC(), IMM(0), Rr(top), VCC()});
+            E(M_V_CNDMASK, {T1, IMM(0), IMM(1), MSK}, true);
+            E(M_V_ADD_U32, {C, C, T1});
+            L(L_WNOGE + id);
+            E(M_V_MOV, {Xr(j), C});
+        }
+        leave(L_DONE);
+    }
     return o;
 }
 
@@ -3481,10 +3815,11 @@ Module build_module(const std::vector<const TapeCode*>& codes,
     }
     const uint32_t n_pin = pinned_cols(n_vars);
     uint32_t maxv = R_COL0 + 8 * n_pin;
-    bool any_div = false, any_lds = false, any_kec = false;
+    bool any_div = false, any_divw = false, any_lds = false, any_kec = false;
     for (const TapeCode* tc : codes) {
         maxv = std::max(maxv, tc->max_vgpr);
         any_div |= tc->calls_div;
+        any_divw |= tc->calls_divw;
         any_lds |= tc->uses_lds;
         any_kec |= tc->calls_kec;
     }
@@ -3674,7 +4009,18 @@ Module build_module(const std::vector<const TapeCode*>& codes,
     if (any_div) {
         line(o, ".p2align 6");
         line(o, "mh_div:");
-        print_list(div_routine(), "mh_dv", o);
+        // the variants' dispatch and sections (labels from 128 up mark them) only where a tape of
+        // this module calls one: the other modules keep the text they had
+        std::vector<MI> dv;
+        bool keep = true;
+        for (const MI& mi : div_routine()) {
+            if (mi.op == M_LABEL && !any_divw) {
+                if (mi.o[0].v == 128 || mi.o[0].v == 129) keep = false;  // L_WHEAD, L_WSEC
+                else if (mi.o[0].v == 1) keep = true;                    // L_UNS
+            }
+            if (keep) dv.push_back(mi);
+        }
+        print_list(dv, "mh_dv", o);
     }
     if (any_kec) {
         line(o, ".p2align 6");
@@ -4049,10 +4395,11 @@ static std::atomic<uint64_t> g_sc_fallbacks{0};
 
 // Staged conjuncts (emit_staged): MH_JIT_STAGE = 0 off, 1 == conjuncts, 2 + ordered compares from
 // exact top limbs, 3 + add / sub with the carry-in left open, 4 + products from their two top
-// columns.
+// columns, 5 + the division subroutine's width-specialised variants (op_div; MH_JIT_DIV=0
+// switches them off with the other division layers).
 static int stage_level() {
     const char* e = std::getenv("MH_JIT_STAGE");  // read per tape: tests switch it in-process
-    return e ? std::min(4, std::max(0, atoi(e))) : 4;
+    return e ? std::min(5, std::max(0, atoi(e))) : 5;
 }
 
 // Inline division fast paths (Emitter::op_div): MH_JIT_DIV = 0 off, 1 dividends known shorter
@@ -4086,9 +4433,13 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
     // those of the called division (the pricing emission keeps the plain sites), so the inline
     // paths leave the conjunct order as it was.
     const int dlevel = div_level();
+    // the division variants follow the build's level (MH_JIT_STAGE), not opt.stage: the parity
+    // build (values, opt.stage = 0) and a tape kept at stage 3 for its registers call them too
+    const bool divw = dlevel > 0 && stage_level() >= 5;
     std::vector<double> cost;
     Emitter e(st, pool, n_vars, opt, nullptr, opt.short_circuit ? &cost : nullptr);
     e.div_ = opt.short_circuit ? 0 : dlevel;
+    e.divw_ = !opt.short_circuit && divw;
     TapeCode tc0 = e.run();
     if (opt.short_circuit) {
         SsaTape sc;
@@ -4101,6 +4452,7 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
                 Emitter e2(sc, pool, n_vars, opt, &check);
                 e2.stage_ = level;
                 e2.div_ = dlevel;
+                e2.divw_ = divw;
                 TapeCode tc = e2.run();
                 if (tc.ok && !e2.stage_rejected_.empty()) {
                     std::vector<uint8_t> skip((size_t)sc.n_vregs, 0);
@@ -4108,6 +4460,7 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
                     Emitter e3(sc, pool, n_vars, opt, &check);
                     e3.stage_ = level;
                     e3.div_ = dlevel;
+                    e3.divw_ = divw;
                     e3.stage_skip_ = &skip;
                     tc = e3.run();
                 }
@@ -4124,6 +4477,7 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
             }
             Emitter e2(sc, pool, n_vars, opt, &check);
             e2.div_ = dlevel;
+            e2.divw_ = divw;
             TapeCode tc = e2.run();
             if (tc.ok) return tc;  // else (register pressure of the new order): source order
             g_sc_fallbacks.fetch_add(1, std::memory_order_relaxed);
@@ -4131,6 +4485,7 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
         if (dlevel > 0 && tc0.ok && tc0.calls_div) {  // source order, with the inline sites
             Emitter e4(st, pool, n_vars, opt);
             e4.div_ = dlevel;
+            e4.divw_ = divw;
             TapeCode tc = e4.run();
             if (tc.ok) return tc;
         }

@@ -143,6 +143,7 @@ struct TapeCode {
     std::vector<MI> code;       // body: root mask in s[S_RES:S_RES+1] (or the root value)
     uint32_t max_vgpr = 0;      // highest VGPR used + 1
     bool calls_div = false;
+    bool calls_divw = false;    // ... through a width-specialised variant (div_routine's marked part)
     bool uses_lds = false;      // variable shifts (the kernel then reserves LDS_WG_BYTES)
     bool calls_kec = false;
     bool root_bool = true;

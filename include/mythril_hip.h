@@ -462,7 +462,8 @@ int32_t mh_eval_values(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape, const m
  * register-class variant among the listed tapes (usually one), one copy back, one sync.       */
 int32_t mh_eval_values_many(mh_ctx* ctx, const mh_tapeset* ts, const uint32_t* tapes, uint32_t n,
                             const mh_assign* as, uint64_t row, uint32_t* out /* [8*n] */);
-/* Kernel launches mh_eval_values_many has made on this context (a test / latency counter).     */
+/* Kernel launches mh_eval_values_many, mh_eval_values_tables and mh_eval_values_jobs have made
+ * on this context (a test / latency counter).                                                  */
 int32_t mh_ctx_eval_launches(const mh_ctx* ctx, uint64_t* launches);
 
 /* ---- table sets (MH_OP_LOOKUP; DESIGN.md §5.2 "table lookup") ---------------------------------
@@ -491,6 +492,49 @@ int32_t mh_eval_values_tables(mh_ctx* ctx, const mh_tapeset* ts, const mh_tables
                               const uint32_t* tapes, uint32_t n, const mh_assign* as,
                               uint64_t row_first, uint64_t row_count,
                               uint32_t* out /* [n][8][row_count] */);
+/* N table sets in one device allocation and one copy (a batch of certifications uploads every
+ * model's tables at once).  Set s has set_tables[s] tables; the per-table arrays (counts, nws,
+ * key_offsets, value_offsets, else_values) are the sets' tables back to back, in set order, and
+ * index the shared keys / values arrays as mh_tables_create's do.  out[s] is a handle like
+ * mh_tables_create's: usable and destroyable on its own, in any order; the device block is freed
+ * with the last handle.  Every set is validated as mh_tables_create validates it before any device
+ * call, and the message names the set: one invalid set creates nothing (every out[s] is NULL).
+ * n_sets == 0 is MH_OK.                                                                          */
+int32_t mh_tables_create_many(mh_ctx* ctx, uint32_t n_sets, const uint32_t* set_tables,
+                              const uint32_t* counts, const uint32_t* nws,
+                              const uint64_t* key_offsets, const uint32_t* keys,
+                              uint64_t n_key_limbs, const uint64_t* value_offsets,
+                              const uint32_t* values, uint64_t n_value_limbs,
+                              const uint32_t* else_values, mh_tables** out /* [n_sets] */);
+
+/* Values of many jobs in one device submission.  A job is mh_eval_values_tables at one row (or,
+ * with tables == NULL, mh_eval_values_many): the roots of its listed tapes at row `row` of `as`,
+ * out[8 * i + k] = limb k of tapes[i]'s root.  Jobs may name different tape sets, table sets and
+ * rows, and MAY share one mh_assign (each reads only its own row, columns by position).
+ *
+ * Contract: for every job `out` equals bit for bit what mh_eval_values_tables(ctx, ts, tables,
+ * tapes, n, as, row, 1, out) writes, or mh_eval_values_many when tables is NULL.  The whole list
+ * is validated before any device call and the message names the job; the refusals are the single
+ * calls': a null or foreign handle, a row or tape id out of bounds, a lookup naming a table the
+ * set lacks or a key of another word count than the table's (MH_E_INVALID); a listed tape with a
+ * lookup in a job without tables, or a kernel variant the buffer's capacity does not fit
+ * (MH_E_UNSUPPORTED).  On any refusal no `out` is touched and nothing is launched.  n_jobs == 0
+ * is MH_OK; more than MH_VALUES_JOBS_MAX jobs is MH_E_INVALID (callers chunk).
+ *
+ * One submission is one upload of descriptors and id lists, one interpreter launch per kernel
+ * variant present among all listed tapes (the table variants included), one copy back and one
+ * sync; mh_ctx_eval_launches grows by the launches made.                                         */
+#define MH_VALUES_JOBS_MAX 256
+typedef struct mh_values_job {
+    const mh_tapeset* ts;
+    const mh_tables*  tables;   /* NULL: no listed tape may hold a lookup */
+    const uint32_t*   tapes;    /* ids, any order, repeats allowed */
+    uint32_t          n;
+    const mh_assign*  as;       /* jobs MAY share one buffer */
+    uint64_t          row;      /* the one row this job reads */
+    uint32_t*         out;      /* [n][8] */
+} mh_values_job;
+int32_t mh_eval_values_jobs(mh_ctx* ctx, const mh_values_job* jobs, uint32_t n_jobs);
 
 /* ---- repair of near-miss rows (no reference counterpart; DESIGN.md §6 "repair") ----------------
  * A query's harvested sets override each other: a row satisfies one conjunct's inversion and

@@ -22,6 +22,7 @@ oracle parity suite pins it.
 """
 from __future__ import annotations
 
+from collections import OrderedDict
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -152,6 +153,13 @@ class ExtModel:
         applications, missing to ``H``; an inverse ``keccak256_N-1`` as the forward table
         reversed, extended by value -> argument for every forward application under `terms`.
         Two arguments with one image leave ``rejected`` set: the row denotes no model."""
+        ext = cls.from_tables(model, model.tables())
+        ext._inverses(model, terms)
+        return ext
+
+    @classmethod
+    def from_tables(cls, model, tabs: dict) -> "ExtModel":
+        """from_model without the inverses, over ``model.tables()`` already answered (`tabs`)."""
         sc = model.schema
         ext = cls()
         for name, v in model.values.items():  # (a symbol only an index term reads is no column)
@@ -159,7 +167,6 @@ class ExtModel:
             if c is None or c.kind == "var":
                 ext.scalars[name] = v
         sym = model.ctx.b.symbols
-        tabs = model.tables()
         for name, got in tabs.items():
             if name in sc.keccak or got is None:
                 continue
@@ -171,18 +178,36 @@ class ExtModel:
             tab = dict(tabs[f][0]) if tabs.get(f) is not None else {}
             tab.update(km.pairs)
             ext.functions[f] = (tab, KeccakRule(km.base))
-        ext._inverses(model, terms)
         return ext
 
     def _inverses(self, model, terms: Sequence[int]) -> None:
+        asked = self._inverse_ask(model, terms)
+        if asked is not None:
+            ask = asked[3]
+            vals = certify_values(model.sieve, model.ctx.b, ask, self) if ask else []
+            self._inverse_answer(model, asked, vals)
+
+    @staticmethod
+    def _inverse_ask(model, terms: Sequence[int]):
+        """None when the context has no keccak inverse; else (the inverses, forward function id
+        -> inverse, the forward applications under `terms`, the terms whose values under this
+        model ``_inverse_answer`` needs: each application's argument, then the application)."""
         b = model.ctx.b
         sym = b.symbols
         inv = [f for f in sym.functions if f.endswith("-1") and f[:-2] in sym.functions]
         if not inv:
-            return
+            return None
         fwd_ids = {sym.functions[f[:-2]][0]: f for f in inv}
         apps = [n for n in _walk(b, terms, host_only=True)
                 if b.nodes[n][0] == Op.UF and b.nodes[n][5] in fwd_ids]
+        ask: List[int] = []
+        for n in apps:
+            ask += [b.nodes[n][2], n]
+        return inv, fwd_ids, apps, ask
+
+    def _inverse_answer(self, model, asked, vals: Sequence[int]) -> None:
+        b = model.ctx.b
+        inv, fwd_ids, apps, _ = asked
         pairs: Dict[str, Dict[int, int]] = {f: {} for f in inv}
         clash = ""
 
@@ -195,13 +220,9 @@ class ExtModel:
         for f in inv:  # the forward table reversed
             for arg, value in self.functions.get(f[:-2], ({}, 0))[0].items():
                 put(f, value, arg)
-        if apps:  # ... and every forward application the terms hold, at its argument's value
-            ask: List[int] = []
-            for n in apps:
-                ask += [b.nodes[n][2], n]
-            vals = certify_values(model.sieve, b, ask, self)
-            for i, n in enumerate(apps):
-                put(fwd_ids[b.nodes[n][5]], vals[2 * i + 1], vals[2 * i])
+        # ... and every forward application the terms hold, at its argument's value
+        for i, n in enumerate(apps):
+            put(fwd_ids[b.nodes[n][5]], vals[2 * i + 1], vals[2 * i])
         for f in inv:
             self.functions[f] = (pairs[f], 0)
         self.rejected = clash
@@ -408,6 +429,294 @@ def certify_values(sieve, b: TapeBuilder, terms: Sequence[int], ext: ExtModel) -
 
 def _nodes(terms) -> List[int]:
     return [t if isinstance(t, int) else t.node for t in terms]
+
+
+# ---- resident, batched certification -----------------------------------------------------------
+CHUNK_ROOTS = 32    # constraints per chunk, in path order: the caching unit
+CHUNK_CACHE = 256   # chunks a Certifier keeps compiled (least recently used closed first)
+
+
+class _Chunk:
+    """Up to CHUNK_ROOTS consecutive constraints of a path, compiled: the tape set of their
+    ext-lowered roots (a term above 256 bits whole, with its slices), the tape set's own column
+    list and its own local table numbering -- what certify_values builds per call, kept."""
+
+    def __init__(self, b: TapeBuilder, ct, columns: List[str], table_ids: List[int],
+                 spans: List[Tuple[int, int]], n_flat: int):
+        self.b = b  # (held: the key's node ids are this builder's)
+        self.ct = ct
+        self.columns = columns
+        self.table_ids = table_ids
+        self.spans = spans
+        self.n_flat = n_flat
+
+    def close(self) -> None:
+        if self.ct is not None:
+            self.ct.close()
+            self.ct = None
+
+
+class Certifier:
+    """certify() for many witnesses in one device pass, with the compiled constraints resident
+    (one per Sieve: ``Sieve.certifier()``).
+
+    A query's constraints are cut, in path order, into chunks of CHUNK_ROOTS; a chunk is compiled
+    once and kept (an LRU of CHUNK_CACHE chunks), so a LASER child's certification finds every
+    full chunk of its parent and compiles at most the last one.  One certification is one
+    ``mh_values_job`` per chunk; N certifications are all their jobs in ceil(jobs / 256)
+    submissions (native.eval_values_jobs), their rows in one upload of one grow-only buffer
+    (job j reads row j, columns by the chunk's own positions) and their table sets in one
+    native.tables_create_many.  ``certify`` / ``certify_values`` stay the checked reference: a
+    verdict here equals theirs."""
+
+    def __init__(self, sieve):
+        self.sieve = sieve
+        self.chunks: "OrderedDict[tuple, _Chunk]" = OrderedDict()
+        self.assign = None
+        # eval_values_jobs submissions: of the table build's asks, of the inverses' forward
+        # applications, and of the constraints ("submissions")
+        self.stats = {"chunk_compiles": 0, "chunk_hits": 0, "ask_submissions": 0,
+                      "inverse_submissions": 0, "submissions": 0}
+
+    def close(self) -> None:
+        for c in self.chunks.values():
+            c.close()
+        self.chunks.clear()
+        if self.assign is not None:
+            self.assign.close()
+            self.assign = None
+
+    # -- chunks ------------------------------------------------------------------------------
+    def _chunk(self, b: TapeBuilder, roots: Sequence[int]) -> _Chunk:
+        from .model import Slicer
+        from .sieve import local_tapeset
+
+        key = (id(b),) + tuple(roots)
+        got = self.chunks.get(key)
+        if got is not None and got.b is b:
+            self.chunks.move_to_end(key)
+            self.stats["chunk_hits"] += 1
+            return got
+        flat: List[int] = []
+        spans = []
+        try:
+            for r in roots:
+                sl = [r] if b.widths[r] <= SLICE else Slicer(b).slices(r)
+                spans.append((len(flat), len(sl)))
+                flat.extend(sl)
+        except CertifyUnsupported:
+            raise
+        except TapeError as e:
+            raise CertifyUnsupported(str(e)) from e
+        columns = _columns(b, flat)
+        ts = local_tapeset(b, flat, columns)
+        table_ids = _local_tables(b, ts, flat)
+        ct = self.sieve.compile(ts)
+        self.stats["chunk_compiles"] += 1
+        if got is not None:
+            got.close()
+        c = self.chunks[key] = _Chunk(b, ct, columns, table_ids, spans, len(flat))
+        self.chunks.move_to_end(key)
+        return c
+
+    def _chunks_of(self, b: TapeBuilder, nodes: Sequence[int]) -> List[_Chunk]:
+        roots = [ext_lower(b, n) for n in nodes]
+        return [self._chunk(b, roots[lo:lo + CHUNK_ROOTS])
+                for lo in range(0, len(roots), CHUNK_ROOTS)]
+
+    def _evict(self) -> None:
+        while len(self.chunks) > CHUNK_CACHE:
+            _, c = self.chunks.popitem(last=False)
+            c.close()
+
+    def _buffer(self, n_cols: int, rows: int):
+        a = self.assign
+        if a is None or a.n_vars < n_cols or a.capacity < rows:
+            n_cols = max(n_cols, a.n_vars if a is not None else 0)
+            rows = max(rows, a.capacity if a is not None else 0, 16)
+            if a is not None:
+                a.close()
+            self.assign = a = self.sieve.ctx.assignments(n_cols, 1 << (rows - 1).bit_length())
+        return a
+
+    # -- API ---------------------------------------------------------------------------------
+    def certify_many(self, models: Sequence, terms_list: Sequence[Sequence],
+                     exts: Optional[Sequence[Optional[ExtModel]]] = None) -> list:
+        """Entry i: the Verdict ``certify(models[i], terms_list[i])`` gives (the failing indices
+        match; an ``ext.rejected`` model gives its rejection verdict), or the CertifyUnsupported
+        / native.Unsupported instance when that one model cannot be judged.  A device or ABI
+        error raises for the whole call.  ``exts[i]``, when given, is certify()'s ``ext``."""
+        out: list = [None] * len(models)
+        nodes_of: list = [None] * len(models)
+        ext_of: list = [None] * len(models)
+        unjudged = (CertifyUnsupported, native.Unsupported)
+        try:
+            # 1. the table build's ask: every model's read-index terms in one table-free submission
+            asks = []
+            for i, (model, terms) in enumerate(zip(models, terms_list)):
+                try:
+                    nodes_of[i] = _nodes(terms)
+                    if exts is not None and exts[i] is not None:
+                        ext_of[i] = exts[i]
+                        continue
+                    parts, keys = model.tables_ask()
+                    res, prep = model._evaluate_prepare(keys, [], True) if keys else ({}, None)
+                    asks.append((i, parts, res, prep))
+                except unjudged as e:
+                    out[i] = e
+            tabs = self._ask(models, asks, out)
+            # 2. the inverses: the forward keccak applications of every model that has an inverse
+            # in a second submission, made only when some model has one
+            inverse = []  # (i, ext, chunks, asked)
+            for i, _, _, _ in asks:
+                if out[i] is not None:
+                    continue
+                try:
+                    ext = ExtModel.from_tables(models[i], tabs[i])
+                    asked = ExtModel._inverse_ask(models[i], nodes_of[i])
+                    if asked is None:
+                        ext_of[i] = ext
+                    elif not asked[3]:
+                        ext._inverse_answer(models[i], asked, [])
+                        ext_of[i] = ext
+                    else:
+                        inverse.append((i, ext, self._chunks_of(models[i].ctx.b, asked[3]), asked))
+                except unjudged as e:
+                    out[i] = e
+            if inverse:
+                vals = self._term_values([(i, ext, chunks) for i, ext, chunks, _ in inverse],
+                                         "inverse_submissions")
+                for (i, ext, _, asked), v in zip(inverse, vals):
+                    ext._inverse_answer(models[i], asked, v)
+                    ext_of[i] = ext
+            # 3. the constraints
+            plans = []  # (i, ext, chunks)
+            for i, model in enumerate(models):
+                if out[i] is not None:
+                    continue
+                try:
+                    ext, nodes = ext_of[i], nodes_of[i]
+                    if ext.rejected:
+                        out[i] = Verdict(False, (), ext.rejected)
+                        continue
+                    b = model.ctx.b
+                    if any(b.widths[n] != BOOL for n in nodes):
+                        raise CertifyUnsupported("certify takes Bool constraints")
+                    if not nodes:
+                        out[i] = Verdict(True)
+                        continue
+                    plans.append((i, ext, self._chunks_of(b, nodes)))
+                except unjudged as e:
+                    out[i] = e
+            if plans:
+                for (i, _, _), flat in zip(plans, self._term_values(plans, "submissions")):
+                    failing = [k for k, v in enumerate(flat) if not v]
+                    out[i] = Verdict(not failing, failing)
+        finally:
+            self._evict()
+        return out
+
+    def _ask(self, models, asks, out) -> Dict[int, dict]:
+        """``Model.tables()`` of every asking model, {model index: tables}: the lowered index
+        terms of all of them as table-free jobs of one submission (what Model._evaluate sends
+        through Sieve.eval_terms one model at a time).  A model whose terms do not compile gets
+        its exception in `out`."""
+        from .sieve import _limbs, local_tapeset
+
+        jobs = []  # (i, compiled tapes, columns, terms)
+        try:
+            for i, _, _, prep in asks:
+                if prep is None:
+                    continue
+                _, flat, columns = prep
+                try:
+                    ct = self.sieve.compile(local_tapeset(models[i].ctx.b, flat, columns))
+                except native.Unsupported as e:
+                    out[i] = e
+                    continue
+                jobs.append((i, ct, columns, len(flat)))
+            vals: Dict[int, List[int]] = {}
+            if jobs:
+                assign = self._buffer(max(len(c) for _, _, c, _ in jobs), len(jobs))
+                soa = np.zeros((assign.n_vars, 8, len(jobs)), dtype=np.uint32)
+                for j, (i, _, columns, _) in enumerate(jobs):
+                    values = models[i].values
+                    for p, name in enumerate(columns):
+                        v = values.get(name, 0)
+                        if v:
+                            soa[p, :, j] = [(v >> (32 * k)) & 0xFFFFFFFF for k in range(8)]
+                assign.upload(soa)
+                got = native.eval_values_jobs(
+                    self.sieve.ctx, [(ct, None, list(range(n)), assign, j)
+                                     for j, (_, ct, _, n) in enumerate(jobs)])
+                self.stats["ask_submissions"] += -(-len(jobs) // native.VALUES_JOBS_MAX)
+                for (i, _, _, n), o in zip(jobs, got):
+                    vals[i] = [_limbs(o[t]) for t in range(n)]
+        finally:
+            for _, ct, _, _ in jobs:
+                ct.close()
+        tabs = {}
+        for i, parts, res, prep in asks:
+            if out[i] is not None:
+                continue
+            at = res if prep is None else models[i]._evaluate_finish(res, prep[0], vals[i])
+            tabs[i] = models[i].tables_answer(parts, at)
+        return tabs
+
+    def _term_values(self, plans, counter: str) -> List[List[int]]:
+        """Per plan (model index, ext, chunks) the values of its chunks' terms, in order."""
+        vals = self._run([(i, ext, c) for i, ext, chunks in plans for c in chunks], counter)
+        out, at = [], 0
+        for _, _, chunks in plans:
+            flat: List[int] = []
+            for c in chunks:
+                v = vals[at]
+                at += 1
+                flat += [sum(v[s + j] << (SLICE * j) for j in range(k)) for s, k in c.spans]
+            out.append(flat)
+        return out
+
+    def certify(self, model, terms, ext: Optional[ExtModel] = None) -> Verdict:
+        """certify(model, terms, ext) through the resident chunks: one model, one submission."""
+        got = self.certify_many([model], [terms], None if ext is None else [ext])[0]
+        if isinstance(got, Exception):
+            raise got
+        return got
+
+    def _run(self, jobs, counter: str) -> List[List[int]]:
+        """Per job (model index, ext, chunk) the values of the chunk's tapes: every job's row in
+        one upload, every table set in one allocation, the jobs in ceil(jobs / 256) submissions."""
+        sieve = self.sieve
+        assign = self._buffer(max(len(c.columns) for _, _, c in jobs), len(jobs))
+        soa = np.zeros((assign.n_vars, 8, len(jobs)), dtype=np.uint32)
+        rows: Dict[int, Dict[str, int]] = {}
+        sets, set_of = [], []
+        for j, (i, ext, c) in enumerate(jobs):
+            row = rows.get(i)
+            if row is None:
+                row = rows[i] = ext.row()
+            for p, name in enumerate(c.columns):
+                v = row.get(name, 0)
+                if v:
+                    soa[p, :, j] = [(v >> (32 * k)) & 0xFFFFFFFF for k in range(8)]
+            if c.table_ids:
+                set_of.append(len(sets))
+                sets.append(ext.tables(c.b, c.table_ids))
+            else:
+                set_of.append(None)  # no lookup in the chunk: a table-free job
+        assign.upload(soa)
+        tables = native.tables_create_many(sieve.ctx, sets) if sets else []
+        try:
+            out = native.eval_values_jobs(
+                sieve.ctx, [(c.ct, None if set_of[j] is None else tables[set_of[j]],
+                             list(range(c.n_flat)), assign, j)
+                            for j, (_, _, c) in enumerate(jobs)])
+            self.stats[counter] += -(-len(jobs) // native.VALUES_JOBS_MAX)
+        finally:
+            for t in tables:
+                t.close()
+        return [[sum(int(o[t, k]) << (32 * k) for k in range(8)) for t in range(len(o))]
+                for o in out]
 
 
 def certify(model, terms, ext: Optional[ExtModel] = None) -> Verdict:

@@ -24,6 +24,7 @@
 #include "dev_isa.h"
 #include "jit.h"
 #include "kernels.h"
+#include "values_plan.h"
 
 constexpr uint32_t kSideStreams = 3;  // with the ctx stream: GPU_MAX_HW_QUEUES (4) queues
 
@@ -273,10 +274,17 @@ struct mh_tapeset {
     std::vector<std::pair<uint32_t, uint32_t>> lookups;
 };
 
+// The device block the sets of one mh_tables_create_many share: freed with the last handle.
+struct TablesBlock {
+    uint32_t* d = nullptr;
+    uint32_t refs = 0;
+};
+
 struct mh_tables {
     mh_ctx* ctx = nullptr;
     uint32_t* d = nullptr;          // the packed set (dev_isa.h layout)
     std::vector<uint32_t> nws;      // key words per table
+    TablesBlock* block = nullptr;   // null: `d` is a pool block of this set alone
 };
 
 struct mh_assign {
@@ -374,6 +382,45 @@ int32_t refuse_tables(const mh_tapeset* ts) {
         return set_err(MH_E_UNSUPPORTED,
                        "the tape set holds table lookups (MH_OP_LOOKUP): only "
                        "mh_eval_values_tables runs it");
+    return MH_OK;
+}
+
+// mh_eval_values_tables / mh_eval_values_jobs: every lookup of the tape set names a table of the
+// set, with the table's key words.
+int32_t check_tables(const mh_ctx* ctx, const mh_tapeset* ts, const mh_tables* tables) {
+    if (tables->ctx != ctx) return set_err(MH_E_INVALID, "table set of another ctx");
+    for (const auto& lk : ts->lookups) {
+        if (lk.first >= tables->nws.size())
+            return set_err(MH_E_INVALID, "a lookup names table " + std::to_string(lk.first) +
+                                             ", the set has " +
+                                             std::to_string(tables->nws.size()));
+        if (lk.second != tables->nws[lk.first])
+            return set_err(MH_E_INVALID, "a lookup's key has " + std::to_string(lk.second) +
+                                             " words, table " + std::to_string(lk.first) +
+                                             " has " + std::to_string(tables->nws[lk.first]));
+    }
+    return MH_OK;
+}
+
+// The batched entry points' pinned staging area and device block (mh_ctx::h_batch / d_batch),
+// grown to `bytes`: a submission goes up in one copy.
+int32_t ctx_batch_bufs(mh_ctx* ctx, size_t bytes) {
+    size_t n = 1 << 16;
+    while (n < bytes) n <<= 1;
+    if (bytes > ctx->h_batch_bytes) {
+        if (ctx->h_batch) MH_HIP(hipHostFree(ctx->h_batch));
+        ctx->h_batch = nullptr;
+        ctx->h_batch_bytes = 0;
+        MH_HIP(hipHostMalloc(&ctx->h_batch, n, hipHostMallocDefault));
+        ctx->h_batch_bytes = n;
+    }
+    if (bytes > ctx->d_batch_bytes) {
+        if (ctx->d_batch) MH_HIP(hipFree(ctx->d_batch));
+        ctx->d_batch = nullptr;
+        ctx->d_batch_bytes = 0;
+        MH_HIP(hipMalloc(&ctx->d_batch, n));
+        ctx->d_batch_bytes = n;
+    }
     return MH_OK;
 }
 
@@ -1050,12 +1097,95 @@ int32_t mh_tables_create(mh_ctx* ctx, uint32_t n_tables, const uint32_t* counts,
     return MH_OK;
 }
 
+int32_t mh_tables_create_many(mh_ctx* ctx, uint32_t n_sets, const uint32_t* set_tables,
+                              const uint32_t* counts, const uint32_t* nws,
+                              const uint64_t* key_offsets, const uint32_t* keys,
+                              uint64_t n_key_limbs, const uint64_t* value_offsets,
+                              const uint32_t* values, uint64_t n_value_limbs,
+                              const uint32_t* else_values, mh_tables** out) {
+    // host-only up to use_device(): one invalid set creates nothing
+    if (!ctx || (n_sets && (!out || !set_tables)))
+        return set_err(MH_E_INVALID, "mh_tables_create_many: null argument");
+    for (uint32_t s = 0; s < n_sets; ++s) out[s] = nullptr;
+    if (n_sets == 0) return MH_OK;
+    std::vector<uint32_t> all, packed;
+    std::vector<size_t> off(n_sets);  // words; every set starts 16-byte aligned
+    std::vector<mh_tables*> made;
+    const auto undo = [&] {
+        for (mh_tables* t : made) {
+            --ctx->children;
+            delete t;
+        }
+    };
+    try {
+        size_t t0 = 0;
+        for (uint32_t s = 0; s < n_sets; ++s) {
+            const uint32_t nt = set_tables[s];
+            std::string err;
+            // set s's tables are entries [t0, t0 + nt) of the per-table arrays
+            if (int32_t r = mh::pack_tables(nt, counts ? counts + t0 : nullptr, nws ? nws + t0 : nullptr,
+                                            key_offsets ? key_offsets + t0 : nullptr, keys,
+                                            n_key_limbs, value_offsets ? value_offsets + t0 : nullptr,
+                                            values, n_value_limbs,
+                                            else_values ? else_values + 8 * t0 : nullptr, packed,
+                                            err)) {
+                undo();
+                return set_err(r, "mh_tables_create_many: set " + std::to_string(s) + ": " + err);
+            }
+            off[s] = all.size();
+            all.insert(all.end(), packed.begin(), packed.end());
+            all.resize((all.size() + 3) & ~(size_t)3, 0u);
+            mh_tables* tb = new mh_tables();
+            tb->ctx = ctx;
+            ++ctx->children;
+            made.push_back(tb);
+            if (nt) tb->nws.assign(nws + t0, nws + t0 + nt);
+            t0 += nt;
+        }
+    } catch (const std::bad_alloc&) {
+        undo();
+        return set_err(MH_E_NOMEM, "host allocation of the table sets");
+    }
+    if (int32_t r = use_device(ctx)) {
+        undo();
+        return r;
+    }
+    TablesBlock* blk = new (std::nothrow) TablesBlock();
+    if (!blk) {
+        undo();
+        return set_err(MH_E_NOMEM, "table block allocation");
+    }
+    hipError_t e = pool_alloc(ctx, &blk->d, all.size() * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(blk->d, all.data(), all.size() * sizeof(uint32_t),
+                           hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // `all` is pageable and local
+    if (e != hipSuccess) {
+        if (blk->d) pool_free(ctx, blk->d);
+        delete blk;
+        undo();
+        return set_err(MH_E_DEVICE, std::string("table sets upload: ") + hipGetErrorString(e));
+    }
+    blk->refs = n_sets;
+    for (uint32_t s = 0; s < n_sets; ++s) {
+        made[s]->block = blk;
+        made[s]->d = blk->d + off[s];
+        out[s] = made[s];
+    }
+    return MH_OK;
+}
+
 int32_t mh_tables_destroy(mh_tables* tb) {
     if (!tb) return MH_OK;
     settle(tb->ctx);
     (void)hipSetDevice(tb->ctx->device);
     if (tb->ctx->stream) (void)hipStreamSynchronize(tb->ctx->stream);
-    pool_free(tb->ctx, tb->d);
+    if (!tb->block) {
+        pool_free(tb->ctx, tb->d);
+    } else if (--tb->block->refs == 0) {
+        pool_free(tb->ctx, tb->block->d);
+        delete tb->block;
+    }
     mh_ctx* ctx = tb->ctx;
     delete tb;
     ctx_unref(ctx);
@@ -1586,27 +1716,7 @@ int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jo
         up_bytes = align(up_bytes + jp[i].L.words * sizeof(uint32_t));
     }
     if (int32_t r = use_device(ctx)) return r;
-    const auto grow = [](size_t have, size_t need) {
-        size_t n = std::max<size_t>(have, 1 << 16);
-        while (n < need) n <<= 1;
-        return n;
-    };
-    if (up_bytes > ctx->h_batch_bytes) {
-        if (ctx->h_batch) MH_HIP(hipHostFree(ctx->h_batch));
-        ctx->h_batch = nullptr;
-        ctx->h_batch_bytes = 0;
-        const size_t n = grow(0, up_bytes);
-        MH_HIP(hipHostMalloc(&ctx->h_batch, n, hipHostMallocDefault));
-        ctx->h_batch_bytes = n;
-    }
-    if (up_bytes > ctx->d_batch_bytes) {
-        if (ctx->d_batch) MH_HIP(hipFree(ctx->d_batch));
-        ctx->d_batch = nullptr;
-        ctx->d_batch_bytes = 0;
-        const size_t n = grow(0, up_bytes);
-        MH_HIP(hipMalloc(&ctx->d_batch, n));
-        ctx->d_batch_bytes = n;
-    }
+    if (int32_t r = ctx_batch_bufs(ctx, up_bytes)) return r;
     void* dres_v = nullptr;
     void* hres_v = nullptr;
     MH_HIP(ctx_dbuf(ctx, std::max<size_t>(res_bytes, 8), &dres_v));
@@ -1751,6 +1861,111 @@ int32_t mh_eval_values_tables(mh_ctx* ctx, const mh_tapeset* ts, const mh_tables
                             "mh_eval_values_tables");
 }
 
+int32_t mh_eval_values_jobs(mh_ctx* ctx, const mh_values_job* jobs, uint32_t n_jobs) {
+    // everything below up to use_device() is host-only: a refused list has queued nothing
+    if (!ctx) return set_err(MH_E_INVALID, "mh_eval_values_jobs: null ctx");
+    if (n_jobs == 0) return MH_OK;
+    if (n_jobs > MH_VALUES_JOBS_MAX)
+        return set_err(MH_E_INVALID, "mh_eval_values_jobs: " + std::to_string(n_jobs) +
+                                         " jobs, more than MH_VALUES_JOBS_MAX (" +
+                                         std::to_string(MH_VALUES_JOBS_MAX) + "): chunk the list");
+    if (!jobs) return set_err(MH_E_INVALID, "mh_eval_values_jobs: null job list");
+    const auto job_err = [](uint32_t i, int32_t code, const std::string& what) {
+        return set_err(code, "mh_eval_values_jobs: job " + std::to_string(i) + ": " + what);
+    };
+    std::vector<mh::values::JobShape> shapes(n_jobs);
+    std::vector<std::vector<uint32_t>> variants(n_jobs);
+    uint64_t slots = 0;
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        const mh_values_job& j = jobs[i];
+        if (int32_t r = check_run_args(ctx, j.ts, 0, 0, j.as, j.row, 1, MH_MODE_COUNT_ALL))
+            return job_err(i, r, g_err);
+        if (j.tables) {
+            if (int32_t r = check_tables(ctx, j.ts, j.tables)) return job_err(i, r, g_err);
+        }
+        if (j.n == 0) continue;
+        if (!j.tapes || !j.out) return job_err(i, MH_E_INVALID, "null tapes / out");
+        variants[i].resize(j.n);
+        for (uint32_t k = 0; k < j.n; ++k) {
+            if (j.tapes[k] >= j.ts->n_tapes) return job_err(i, MH_E_INVALID, "tape id out of bounds");
+            const mh_tape_info& ti = j.ts->info[j.tapes[k]];
+            if (!j.tables && (ti.features & F_TABLE))
+                return job_err(i, MH_E_UNSUPPORTED,
+                               "tape " + std::to_string(j.tapes[k]) +
+                                   " holds a table lookup (MH_OP_LOOKUP) and the job has no tables");
+            const uint32_t v = mh::variant_of(ti.n_regs, ti.features);
+            if (!mh::variant_fits(v, j.as->stride)) {
+                (void)refuse_capacity(j.as->stride);
+                return job_err(i, MH_E_UNSUPPORTED, g_err);
+            }
+            variants[i][k] = v;
+        }
+        shapes[i].ids = j.tapes;
+        shapes[i].variants = variants[i].data();
+        shapes[i].n = j.n;
+        slots += j.n;
+    }
+    if (slots == 0) return MH_OK;
+    if (slots * 8 >= (1ull << 31))
+        return set_err(MH_E_INVALID, "mh_eval_values_jobs: values of 2^31 words or more in one call");
+    const mh::values::Plan plan = mh::values::plan(shapes.data(), n_jobs);
+    // the upload block: segments' KParams | block table | sorted ids
+    const auto align = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_seg = 0;
+    const size_t o_blk = align(o_seg + plan.segments.size() * sizeof(mh::KParams));
+    const size_t o_ids = align(o_blk + plan.blocks.size() * sizeof(mh::batch::BlockEntry));
+    const size_t up_bytes = align(o_ids + plan.ids.size() * sizeof(uint32_t));
+    const size_t val_bytes = (size_t)slots * 8 * sizeof(uint32_t);
+    if (int32_t r = use_device(ctx)) return r;
+    if (int32_t r = ctx_batch_bufs(ctx, up_bytes)) return r;
+    void* dval_v = nullptr;
+    void* hval_v = nullptr;
+    MH_HIP(ctx_dbuf(ctx, val_bytes, &dval_v));
+    MH_HIP(ctx_hbuf(ctx, val_bytes, &hval_v));
+    uint32_t* const dval = static_cast<uint32_t*>(dval_v);
+    const uint32_t* const hval = static_cast<const uint32_t*>(hval_v);
+    char* const hb = static_cast<char*>(ctx->h_batch);
+    char* const db = static_cast<char*>(ctx->d_batch);
+    const uint32_t* const d_ids = reinterpret_cast<const uint32_t*>(db + o_ids);
+    mh::KParams* h_seg = reinterpret_cast<mh::KParams*>(hb + o_seg);
+    for (size_t si = 0; si < plan.segments.size(); ++si) {
+        const mh::values::Segment& sg = plan.segments[si];
+        const mh_values_job& j = jobs[sg.job];
+        // values mode over one row: the count-mode bookkeeping (first_hit / hit_count) has no
+        // reader, and sieve_body skips a null array
+        mh::KParams p = make_params(j.ts, 0, j.as, j.row, 1, 0, MH_MODE_COUNT_ALL);
+        p.tables = j.tables ? j.tables->d : nullptr;
+        p.tape_ids = d_ids + sg.first;
+        p.n_ids = sg.n_ids;
+        p.values_out = dval + 8 * (size_t)sg.first;
+        h_seg[si] = p;
+    }
+    std::memcpy(hb + o_blk, plan.blocks.data(), plan.blocks.size() * sizeof(mh::batch::BlockEntry));
+    std::memcpy(hb + o_ids, plan.ids.data(), plan.ids.size() * sizeof(uint32_t));
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, s);
+    const mh::batch::BlockEntry* d_blk = reinterpret_cast<const mh::batch::BlockEntry*>(db + o_blk);
+    uint32_t launches = 0;
+    for (const auto& l : plan.launches)
+        if (e == hipSuccess) {
+            e = mh::launch_sieve_batch(reinterpret_cast<const mh::KParams*>(db + o_seg),
+                                       d_blk + l.first, l.count, l.variant, s);
+            ++launches;
+        }
+    if (e == hipSuccess) e = hipMemcpyAsync(hval_v, dval, val_bytes, hipMemcpyDeviceToHost, s);
+    // the staging area is read by the queued copy: wait even after an error
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess)
+        return set_err(MH_E_DEVICE, std::string("mh_eval_values_jobs: ") + hipGetErrorString(e));
+    for (uint32_t i = 0; i < n_jobs; ++i)
+        for (uint32_t q = plan.job_first[i]; q < plan.job_first[i + 1]; ++q)
+            std::memcpy(jobs[i].out + 8 * (size_t)plan.pos[q], hval + 8 * (size_t)q,
+                        8 * sizeof(uint32_t));
+    ctx->eval_launches += launches;
+    return MH_OK;
+}
+
 }  // extern "C"
 
 // mh_eval_values_many (tables == null: one row, tapes with lookups refused) and
@@ -1763,17 +1978,7 @@ static int32_t eval_values_rows(mh_ctx* ctx, const mh_tapeset* ts, const mh_tabl
     if (!tables) {
         if (int32_t r = refuse_tables(ts)) return r;
     } else {
-        if (tables->ctx != ctx) return set_err(MH_E_INVALID, "table set of another ctx");
-        for (const auto& lk : ts->lookups) {
-            if (lk.first >= tables->nws.size())
-                return set_err(MH_E_INVALID, "a lookup names table " + std::to_string(lk.first) +
-                                                 ", the set has " +
-                                                 std::to_string(tables->nws.size()));
-            if (lk.second != tables->nws[lk.first])
-                return set_err(MH_E_INVALID, "a lookup's key has " + std::to_string(lk.second) +
-                                                 " words, table " + std::to_string(lk.first) +
-                                                 " has " + std::to_string(tables->nws[lk.first]));
-        }
+        if (int32_t r = check_tables(ctx, ts, tables)) return r;
     }
     if (n == 0 || row_count == 0) return MH_OK;
     if (!tapes || !out) return set_err(MH_E_INVALID, "null tapes / out");

@@ -83,7 +83,10 @@ hipError_t launch_generate_guided(uint32_t* assign, uint64_t stride, uint64_t fi
                                   hipStream_t stream);
 // A batched round (mh_query_round_many; the tables are batch_plan.h's, on the device, read only).
 // Interpreter: workgroup i of the launch runs blocks[i] = {segment, row block, tape slice, slices}
-// with segs[segment]; `variant` < kFirstTableVariant serves every segment of the launch.
+// with segs[segment]; `variant` serves every segment of the launch.  A round's launches are
+// table-free (`variant` < kFirstTableVariant); mh_eval_values_jobs (values_plan.h: one-row
+// segments in values mode, row block 0) also launches the table variants, whose segments each
+// carry their own `tables`.
 hipError_t launch_sieve_batch(const KParams* segs, const batch::BlockEntry* blocks,
                               uint32_t n_blocks, uint32_t variant, hipStream_t stream);
 // Generator: what launch_generate_guided takes, per job (rows [0, count) of the buffer).

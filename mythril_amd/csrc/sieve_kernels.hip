@@ -17,7 +17,7 @@
 //
 // Kernel variants (kernels.h variant_of): NR in {7, 9, 15} x {asm only, + C++ overflow
 // predicates / unpinned columns, + keccak, + keccak/EVM}, and per NR one with every handler and
-// the table lookup (D_LOOKUP; mh_eval_values_tables only);
+// the table lookup (D_LOOKUP; mh_eval_values_tables and mh_eval_values_jobs only);
 // mh_run launches one variant per non-empty bucket of tapes, so a tape set's simple tapes run
 // with the register budget (and occupancy) they need rather than the worst tape's.
 #include <hip/hip_runtime.h>
@@ -692,6 +692,9 @@ __attribute__((amdgpu_waves_per_eu(sieve_min_waves(NR, FEAT), 8))) sieve_kernel(
 // so the loads are scalar and the parameters live in SGPRs as a kernel argument's do; the body
 // -- LDS chunking, the FIRST_HIT early exit, one atomic per tape per workgroup -- is unchanged.
 // One-wave workgroups: the short-run shape sieve_block() picks for <= kShortRows rows.
+// mh_eval_values_jobs drives the same kernels in values mode (a segment = one job's tapes of one
+// variant over ONE row, values_plan.h), the F_TABLE feature class included: a segment's KParams
+// names its own table set, so jobs under different tables share a launch.
 template <int NR, int FEAT>
 __global__ void __launch_bounds__(64)
 __attribute__((amdgpu_waves_per_eu(sieve_min_waves(NR, FEAT), 8)))
@@ -800,7 +803,8 @@ hipError_t launch_sieve_batch(const KParams* segs, const batch::BlockEntry* bloc
                               uint32_t n_blocks, uint32_t variant, hipStream_t stream) {
     if (n_blocks == 0) return hipSuccess;
     constexpr int kCplx = F_CPLX, kKec = F_CPLX | F_KECCAK, kAll = F_CPLX | F_KECCAK | F_EVM;
-    switch (variant) {  // the twelve non-table variants: a batch never holds a lookup
+    constexpr int kTab = kAll | F_TABLE;
+    switch (variant) {  // 12..14: mh_eval_values_jobs only, a batched round never holds a lookup
         case 0: return launch_batch_variant<MH_NR_SMALL, 0>(segs, blocks, n_blocks, stream);
         case 1: return launch_batch_variant<MH_NR_SMALL, kCplx>(segs, blocks, n_blocks, stream);
         case 2: return launch_batch_variant<MH_NR_SMALL, kKec>(segs, blocks, n_blocks, stream);
@@ -813,6 +817,9 @@ hipError_t launch_sieve_batch(const KParams* segs, const batch::BlockEntry* bloc
         case 9: return launch_batch_variant<MH_NR_MAX, kCplx>(segs, blocks, n_blocks, stream);
         case 10: return launch_batch_variant<MH_NR_MAX, kKec>(segs, blocks, n_blocks, stream);
         case 11: return launch_batch_variant<MH_NR_MAX, kAll>(segs, blocks, n_blocks, stream);
+        case 12: return launch_batch_variant<MH_NR_SMALL, kTab>(segs, blocks, n_blocks, stream);
+        case 13: return launch_batch_variant<MH_NR_MID, kTab>(segs, blocks, n_blocks, stream);
+        case 14: return launch_batch_variant<MH_NR_MAX, kTab>(segs, blocks, n_blocks, stream);
         default: return hipErrorInvalidValue;
     }
 }

@@ -60,6 +60,9 @@ _config = {
     "certify": None,    # certify every witness against the original constraints (certify.py)
                         # before the verifier sees it; None: the SIEVE_CERTIFY environment
                         # variable ("1" turns it on), off by default
+    "certify_resident": None,  # sieve_model's own certification goes through the sieve's
+                               # resident Certifier (certify.py); None: SIEVE_CERTIFY_RESIDENT=1
+                               # turns it on, off by default
 }
 
 
@@ -71,12 +74,17 @@ class SieveUnavailable(RuntimeError):
 def configure(*, fallback: Optional[Callable] = None, verify: Optional[Callable] = None,
               to_terms: Optional[Callable] = None, enabled: Optional[bool] = None,
               log_writer: Optional[Callable] = None, fallback_logs: Optional[bool] = None,
-              certify: Optional[bool] = None, **sieve_kwargs) -> None:
+              certify: Optional[bool] = None, certify_resident: Optional[bool] = None,
+              **sieve_kwargs) -> None:
     """Set the fallback solver, the witness verifier, the term importer and sieve options.
     ``certify=True`` (or SIEVE_CERTIFY=1) certifies every witness against the original
-    constraints on the device before it is returned or verified (certify.py)."""
+    constraints on the device before it is returned or verified (certify.py);
+    ``certify_resident=True`` (or SIEVE_CERTIFY_RESIDENT=1) does so through the sieve's resident
+    Certifier, which keeps a path's compiled constraints between queries."""
     if certify is not None:
         _config["certify"] = bool(certify)
+    if certify_resident is not None:
+        _config["certify_resident"] = bool(certify_resident)
     if fallback is not None:
         _config["fallback"] = fallback
     if log_writer is not None:
@@ -104,6 +112,14 @@ def certification_on() -> bool:
     return os.environ.get("SIEVE_CERTIFY", "") == "1" if c is None else c
 
 
+def certify_resident_on() -> bool:
+    """configure(certify_resident=...) when set, else SIEVE_CERTIFY_RESIDENT=1; off by default."""
+    import os
+
+    c = _config["certify_resident"]
+    return os.environ.get("SIEVE_CERTIFY_RESIDENT", "") == "1" if c is None else c
+
+
 def _takes_timeout(fn) -> bool:
     try:
         ps = inspect.signature(fn).parameters.values()
@@ -123,7 +139,8 @@ def _verify(verify, constraints, m, left):
 def reset() -> None:
     """Back to defaults (tests, plugin stop)."""
     _config.update(fallback=None, verify=None, to_terms=None, log_writer=None,
-                   fallback_logs=False, sieve_kwargs={}, enabled=True, certify=None)
+                   fallback_logs=False, sieve_kwargs={}, enabled=True, certify=None,
+                   certify_resident=None)
     close_sieve()
     clear_prefetched()
     get_model.cache_clear()
@@ -224,11 +241,21 @@ def _parked() -> "OrderedDict":
     return t
 
 
+def _parked_verdicts() -> dict:
+    """This thread's parked verdicts (prefetch with certification on): key -> (term context,
+    certify_many's entry for the parked witness).  Cleared with the parked answers."""
+    t = getattr(_tls, "parked_verdicts", None)
+    if t is None:
+        t = _tls.parked_verdicts = {}
+    return t
+
+
 def clear_prefetched() -> None:
     """Drop this thread's parked answers (configure, reset, forget_witnesses do)."""
-    t = getattr(_tls, "parked", None)
-    if t:
-        t.clear()
+    for name in ("parked", "parked_verdicts"):
+        t = getattr(_tls, name, None)
+        if t:
+            t.clear()
 
 
 def prefetch(queries) -> int:
@@ -239,7 +266,11 @@ def prefetch(queries) -> int:
     answer is parked under the query's key; sieve_model looks there before it runs a round of
     its own: a parked witness goes through certification and the verifier as any other, a parked
     miss goes to the fallback without a device round (and the fallback's model is still
-    learnt).  A query with a Python False is UNSAT without the sieve and is skipped; other bools
+    learnt).  With certification on, the witnesses found are certified here in one
+    Certifier.certify_many and each verdict is parked beside its answer: sieve_model then uses it
+    instead of certifying again (the counters move there, as they do today); a rejected witness
+    is dropped from the sieve's parent-witness table at once.  If that certification errors, the
+    answers stay parked without verdicts and take the ordinary path.  A query with a Python False is UNSAT without the sieve and is skipped; other bools
     are dropped, as in get_model.  The whole list shares args.solver_timeout.  Never raises: any
     error leaves the table as it was and the queries to the ordinary path.  Returns the number
     of answers parked."""
@@ -274,12 +305,41 @@ def prefetch(queries) -> int:
     except Exception as e:  # noqa: BLE001 - prefetching never changes an answer
         log.debug("prefetch left to the ordinary path: %s", e)
         return 0
+    verdicts = _parked_verdicts()
     for key, entry in fresh:
         table[key] = entry
         table.move_to_end(key)
+        verdicts.pop(key, None)
+    if certification_on():
+        verdicts.update(_certify_parked(s, fresh))
     while len(table) > PARKED_MAX:
-        table.popitem(last=False)
+        verdicts.pop(table.popitem(last=False)[0], None)
     return len(fresh)
+
+
+def _certify_parked(s, fresh) -> dict:
+    """key -> (term context, verdict) for the witnesses among the freshly parked answers: one
+    Certifier.certify_many for all of them.  Never raises: on an error nothing is verdicted."""
+    from .model import Model
+
+    found = [(key, e) for key, e in fresh if e[1] is not None]
+    if not found:
+        return {}
+    conv = _config["to_terms"]
+    importer = conv if hasattr(conv, "term") else None
+    try:
+        models = [Model(s, ctx, w.schema, w.values, w.index, importer=importer)
+                  for _, (ctx, w, _, _) in found]
+        got = s.certifier().certify_many(models, [list(key) for key, _ in found])
+    except Exception as e:  # noqa: BLE001 - the witnesses are certified one by one later
+        log.debug("prefetch: certification left to the ordinary path: %s", e)
+        return {}
+    out = {}
+    for (key, (ctx, _, _, _)), v in zip(found, got):
+        out[key] = (ctx, v)
+        if not isinstance(v, Exception) and not v:
+            s.witnesses.pop(key, None)  # does not seed the query's children
+    return out
 
 
 def sieve_model(constraints, timeout_ms: Optional[float] = None):
@@ -298,6 +358,11 @@ def sieve_model(constraints, timeout_ms: Optional[float] = None):
         budget = None if timeout_ms is None else max(timeout_ms, 0.0) / 1000.0
         parked = getattr(_tls, "parked", None)
         entry = parked.pop(key, None) if parked else None
+        pv = getattr(_tls, "parked_verdicts", None)
+        pv = pv.pop(key, None) if pv else None
+        parked_verdict = None
+        if entry is not None and entry[0] is ctx and pv is not None and pv[0] is ctx:
+            parked_verdict = pv[1]
         if entry is not None and entry[0] is ctx:
             # answered by prefetch(): no round here; a miss leaves the sieve as solve() would
             # have, so the fallback's model of it is learnt
@@ -330,7 +395,14 @@ def sieve_model(constraints, timeout_ms: Optional[float] = None):
         from .native import Unsupported
 
         try:
-            verdict = certify(m, terms)
+            if parked_verdict is not None:  # certified by prefetch(), with the other answers
+                if isinstance(parked_verdict, Exception):
+                    raise parked_verdict
+                verdict = parked_verdict
+            elif certify_resident_on():
+                verdict = s.certifier().certify(m, terms)
+            else:
+                verdict = certify(m, terms)
         except (CertifyUnsupported, Unsupported) as e:
             stats.sieve_uncertified += 1
             log.debug("sieve witness not certified: %s", e)

@@ -176,6 +176,14 @@ class Model:
         """{name: table(name)} for `names` (default: every array and function symbol the schema
         has columns or cells of, keccak functions included), the read indices of ALL of them
         evaluated in one device batch (``table`` costs a batch per symbol)."""
+        parts, keys = self.tables_ask(names)
+        at = self._evaluate(keys, [], True) if keys else {}
+        return self.tables_answer(parts, at)
+
+    def tables_ask(self, names: Optional[Sequence[str]] = None):
+        """The "ask" half of ``tables``: (what ``tables_answer`` needs, the index terms whose
+        values under the witness it needs -- nodes, each once).  certify.Certifier evaluates many
+        models' asks in one device submission."""
         from .lower import READ_KINDS
 
         sc = self.schema
@@ -194,7 +202,10 @@ class Model:
             reads = sorted((c for c in cols if c.kind in READ_KINDS), key=lambda c: c.key)
             parts[name] = (cells, els, reads)
             keys += [c.key for c in reads]
-        at = self._evaluate(list(dict.fromkeys(keys)), [], True) if keys else {}
+        return parts, list(dict.fromkeys(keys))
+
+    def tables_answer(self, parts, at: dict) -> dict:
+        """The "answer" half of ``tables``: `at` maps every asked index term to its value."""
         out = {}
         for name, (cells, els, reads) in parts.items():
             if cells is None and not els and not reads:
@@ -280,6 +291,17 @@ class Model:
     def _evaluate(self, nodes: Sequence[int], extra: Sequence[int], mc: bool) -> dict:
         """{node: value or _UNEVALUATED} of `nodes` (requested: a lowering failure with model
         completion raises) and `extra` (speculated: failures are left out)."""
+        res, prep = self._evaluate_prepare(nodes, extra, mc)
+        if prep is None:
+            return res
+        spans, flat, columns = prep
+        vals = self.sieve.eval_terms(self.ctx.b, flat, columns, self.values,
+                                     resident=self._resident)
+        return self._evaluate_finish(res, spans, vals)
+
+    def _evaluate_prepare(self, nodes: Sequence[int], extra: Sequence[int], mc: bool):
+        """``_evaluate`` up to the device: (the values already decided, (spans, the lowered
+        256-bit terms to evaluate, their columns) or None when nothing is left to evaluate)."""
         from copy import deepcopy
 
         from .lower import Lowering, LoweringUnsupported, node_columns, var_names
@@ -313,7 +335,7 @@ class Model:
                 continue
             todo.append((n, r))
         if not todo:
-            return res
+            return res, None
         columns = list(schema.columns) or ["__ground__"]
         if columns == ["__ground__"]:
             b.var("__ground__", 1)
@@ -330,7 +352,11 @@ class Model:
                 sl = Slicer(b).slices(r)
                 spans.append((n, width, len(flat), len(sl)))
                 flat.extend(sl)
-        vals = self.sieve.eval_terms(b, flat, columns, self.values, resident=self._resident)
+        return res, (spans, flat, columns)
+
+    @staticmethod
+    def _evaluate_finish(res: dict, spans, vals) -> dict:
+        """``_evaluate`` after the device: `vals` are the values of the prepared terms."""
         for n, width, at, k in spans:
             if width == BOOL:
                 res[n] = bool(vals[at])

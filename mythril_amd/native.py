@@ -89,6 +89,10 @@ SIGNATURES = {
     "mh_tables_destroy": (C.c_int32, [_vp]),
     "mh_eval_values_tables": (C.c_int32, [_vp, _vp, _vp, _u32p, C.c_uint32, _vp, C.c_uint64,
                                           C.c_uint64, _u32p]),
+    "mh_tables_create_many": (C.c_int32, [_vp, C.c_uint32, _u32p, _u32p, _u32p, _u64p, _u32p,
+                                          C.c_uint64, _u64p, _u32p, C.c_uint64, _u32p,
+                                          C.POINTER(_vp)]),
+    "mh_eval_values_jobs": (C.c_int32, [_vp, _vp, C.c_uint32]),
     "mh_tapes_jit": (C.c_int32, [_vp, C.c_uint32, C.c_uint32]),
     "mh_tapes_jit_info": (C.c_int32, [_vp, _vp]),
     "mh_tapes_jit_code_id": (C.c_int32, [_vp, _u64p]),
@@ -241,6 +245,18 @@ class RoundJob(C.Structure):
 
 
 ROUND_MANY_MAX = 256  # MH_ROUND_MANY_MAX
+
+
+class ValuesJob(C.Structure):
+    """mh_values_job (include/mythril_hip.h)."""
+
+    _fields_ = [
+        ("ts", _vp), ("tables", _vp), ("tapes", _u32p), ("n", C.c_uint32), ("as_", _vp),
+        ("row", C.c_uint64), ("out", _u32p),
+    ]
+
+
+VALUES_JOBS_MAX = 256  # MH_VALUES_JOBS_MAX
 
 _lib: Optional[C.CDLL] = None
 
@@ -1244,6 +1260,53 @@ def eval_values_tables(ctx: "Context", tapes: "CompiledTapes", tables: Tables,
     _check(ctx.lib.mh_eval_values_tables(ctx.h, tapes.h, tables.h, _ptr(ids_a), len(ids_a),
                                          assign.h, row_first, row_count, _ptr(out)))
     return out[:len(ids_a), :, :row_count]
+
+
+def tables_create_many(ctx: "Context",
+                       sets: Sequence[Sequence[Tuple[dict, int, int]]]) -> List[Tables]:
+    """One Tables per entry of `sets` (each what tables_create takes), in one device allocation
+    and one copy (mh_tables_create_many).  Every handle closes on its own; the device block goes
+    with the last.  One invalid set creates none."""
+    if not sets:
+        return []
+    flat = [t for s in sets for t in s]
+    counts, nws, koffs, keys, voffs, vals, elses, n_keys, n_vals = pack_tables(flat)
+    per_set = np.ascontiguousarray([len(s) for s in sets], dtype=np.uint32)
+    hs = (C.c_void_p * len(sets))()
+    _check(ctx.lib.mh_tables_create_many(ctx.h, len(sets), _ptr(per_set), _ptr(counts), _ptr(nws),
+                                         _ptr(koffs, C.c_uint64), _ptr(keys), n_keys,
+                                         _ptr(voffs, C.c_uint64), _ptr(vals), n_vals,
+                                         _ptr(elses), hs))
+    out = []
+    for h in hs:
+        tb = Tables.__new__(Tables)
+        tb.ctx = ctx
+        tb.h = C.c_void_p(h)
+        out.append(tb)
+    return out
+
+
+def eval_values_jobs(ctx: "Context", jobs: Sequence[tuple]) -> List[np.ndarray]:
+    """Root values of many jobs in one device submission (mh_eval_values_jobs).  A job is
+    (tapes, tables or None, ids, assign, row): what eval_values_tables(ctx, tapes, tables, ids,
+    assign, row, 1) takes, or eval_values_many when tables is None; jobs may share one `assign`.
+    Returns per job u32 [len(ids), 8], equal to the single call's.  Lists beyond VALUES_JOBS_MAX
+    jobs go up in chunks."""
+    out: List[np.ndarray] = []
+    for lo in range(0, len(jobs), VALUES_JOBS_MAX):
+        chunk = jobs[lo:lo + VALUES_JOBS_MAX]
+        arr = (ValuesJob * len(chunk))()
+        keep = []
+        for k, (tapes, tables, ids, assign, row) in enumerate(chunk):
+            ids_a = np.ascontiguousarray(ids, dtype=np.uint32)
+            vals = np.zeros((max(len(ids_a), 1), 8), dtype=np.uint32)
+            arr[k] = ValuesJob(tapes.h, tables.h if tables is not None else None,
+                               _ptr(ids_a) if len(ids_a) else None, len(ids_a), assign.h, row,
+                               _ptr(vals))
+            keep.append((ids_a, vals))
+        _check(ctx.lib.mh_eval_values_jobs(ctx.h, arr, len(chunk)))
+        out.extend(vals[:len(ids_a)] for ids_a, vals in keep)
+    return out
 
 
 # ---- repair of near-miss rows (include/mythril_hip.h mh_conjuncts_* / mh_repair_*) -------------

@@ -543,8 +543,21 @@ class Sieve:
         # calls; and the last call's per-query records
         self.round_pool: Dict[int, List[native.Assignments]] = {}
         self.last_many: List[Dict] = []
+        self._certifier = None  # certify.Certifier, made on first use (certifier())
+
+    def certifier(self):
+        """This sieve's resident certifier (certify.Certifier): made on first use, closed with
+        the sieve."""
+        if self._certifier is None:
+            from .certify import Certifier
+
+            self._certifier = Certifier(self)
+        return self._certifier
 
     def close(self) -> None:
+        if self._certifier is not None:
+            self._certifier.close()
+            self._certifier = None
         if self.repairer is not None:
             self.repairer.close()
             self.repairer = None

@@ -20,6 +20,17 @@ queries; planted LASER paths.  ``solve`` is the hit itself, so certification off
 alone.  One JSON line per workload, medians in milliseconds.
 
     python scripts/certify_cost.py [path_shape=ether_thief] [path_length=400]
+
+``--many N`` compares, on the same witnesses, sequential ``certify`` with one
+``Certifier.certify_many`` over N of them (certify.py "resident, batched certification"), on the
+LASER-shaped queries' prefixes and the planted LASER paths: ms per certified hit, the two paths
+interleaved in every repetition, the batched one with a fresh Certifier (``many_cold``: batching
+alone, every chunk compiled) and with its chunks kept (``many_resident``).  ``--resident``
+compares them query by query on the grown path's last 8 queries, the Certifier having seen the
+path's earlier queries as under LASER.  No stage wrappers are installed in these modes.
+
+    python scripts/certify_cost.py --many 64
+    python scripts/certify_cost.py --resident [path_shape] [path_length]
 """
 import gc
 import json
@@ -89,9 +100,117 @@ def med(rows):
     return out
 
 
+def hits_of(s, ctx, nodes, first=1):
+    """(model, constraints) of every prefix of `nodes` the sieve answers, in LASER order."""
+    out = []
+    for k in range(1, len(nodes) + 1):
+        w = s.solve(ctx.b, nodes[:k], key=tuple(nodes[:k]))
+        if w is not None and k >= first:
+            out.append((Model(s, ctx, w.schema, w.values, w.index), nodes[:k]))
+    return out
+
+
+def spread(xs):
+    return dict(median=round(statistics.median(xs), 3), min=round(min(xs), 3),
+                max=round(max(xs), 3))
+
+
+def compare_many(s, pool, n, workload, reps=7):
+    """ms per certified hit over `n` witnesses of `pool` (cycled when it holds fewer)."""
+    group = [pool[i % len(pool)] for i in range(n)]
+    models, terms = [m for m, _ in group], [t for _, t in group]
+    seq, cold, res = [], [], []
+    resident = C.Certifier(s)
+    resident.certify_many(models, terms)
+    for _ in range(reps):
+        gc.collect()
+        t0 = time.perf_counter()
+        want = [C.certify(m, t) for m, t in group]
+        seq.append((time.perf_counter() - t0) * 1e3 / n)
+        fresh = C.Certifier(s)
+        t0 = time.perf_counter()
+        got = fresh.certify_many(models, terms)
+        cold.append((time.perf_counter() - t0) * 1e3 / n)
+        fresh.close()
+        t0 = time.perf_counter()
+        again = resident.certify_many(models, terms)
+        res.append((time.perf_counter() - t0) * 1e3 / n)
+        assert [bool(v) for v in want] == [bool(v) for v in got] == [bool(v) for v in again]
+    resident.close()
+    print(json.dumps(dict(workload=workload, many=n, witnesses=len(pool), reps=reps,
+                          unit="ms per certified hit", sequential=spread(seq),
+                          many_cold=spread(cold), many_resident=spread(res),
+                          constraints_median=statistics.median(len(t) for t in terms))),
+          flush=True)
+
+
+def main_many(n):
+    s = Sieve()
+    ctx, qs = queries()
+    pool = []
+    for name, _ in qs:
+        if not name.startswith("unsat"):
+            pool += hits_of(s, ctx, [c.node for c in dict(qs)[name]])
+    compare_many(s, pool, n, "laser-shaped queries, every prefix hit")
+    pool = []
+    for seed in range(10):
+        ctx, cs, _, _ = planted_path("laser", seed, 16)
+        pool += hits_of(s, ctx, [c.node for c in cs], first=3)
+    compare_many(s, pool, n, "planted LASER paths 10 x 16, prefixes >= 3")
+    s.close()
+
+
+def main_resident(shape, length, reps=5):
+    s = Sieve()
+    ctx, cs = grow(shape, length)
+    nodes = [c.node for c in cs]
+    # the hits among the last 9 prefixes: the first is the parent LASER leaves certified behind
+    # it, the others are measured
+    tail = hits_of(s, ctx, nodes, first=len(nodes) - 8)
+    prime, last = tail[:1], tail[1:]
+    resident = C.Certifier(s)
+    t0 = time.perf_counter()
+    for m, t in prime:
+        resident.certify(m, t)
+    prime_ms = (time.perf_counter() - t0) * 1e3
+    per_query = []
+    for m, t in last:
+        seq, res = [], []
+        compiles = resident.stats["chunk_compiles"]
+        for r in range(reps):
+            gc.collect()
+            t0 = time.perf_counter()
+            want = C.certify(m, t)
+            seq.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            got = resident.certify(m, t)
+            res.append((time.perf_counter() - t0) * 1e3)
+            assert bool(want) == bool(got)
+        # the first resident run is the LASER child's: it compiles the new chunk (at most one)
+        per_query.append(dict(constraints=len(t), sequential=spread(seq),
+                              resident_first=round(res[0], 3), resident_again=spread(res[1:]),
+                              chunks_compiled=resident.stats["chunk_compiles"] - compiles))
+    print(json.dumps(dict(workload="%s-%d in LASER order, last %d hits" % (shape, length, len(last)),
+                          unit="ms per certification", prime_parent_ms=round(prime_ms, 3),
+                          sequential_median=round(statistics.median(
+                              q["sequential"]["median"] for q in per_query), 3),
+                          resident_first_median=round(statistics.median(
+                              q["resident_first"] for q in per_query), 3),
+                          resident_again_median=round(statistics.median(
+                              q["resident_again"]["median"] for q in per_query), 3),
+                          queries=per_query)), flush=True)
+    resident.close()
+    s.close()
+
+
 def main():
-    shape = sys.argv[1] if len(sys.argv) > 1 else "ether_thief"
-    length = int(sys.argv[2]) if len(sys.argv) > 2 else 400
+    argv = [a for a in sys.argv[1:] if not a.startswith("--")]
+    if "--many" in sys.argv:
+        return main_many(int(sys.argv[sys.argv.index("--many") + 1]))
+    shape = argv[0] if argv else "ether_thief"
+    length = int(argv[1]) if len(argv) > 1 else 400
+    if "--resident" in sys.argv:
+        return main_resident(shape, length)
     install()
     s = Sieve()
     ctx, qs = queries()

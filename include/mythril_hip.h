@@ -614,6 +614,76 @@ int32_t mh_repair_mutate(mh_repair* r, const mh_assign* src, mh_assign* dst, con
                          const uint32_t* conj_cols, uint32_t n_conjuncts, uint32_t per,
                          uint32_t flags, uint64_t seed, uint64_t global_base);
 
+/* ---- decision by enumeration (no reference counterpart; DESIGN.md §6 "Decision by enumeration") --
+ * A group whose columns all have small provable domains is decided exactly: the device writes the
+ * cross product of the domains in order, the interpreter runs the group's tape over it, and the
+ * group has a witness (the smallest row) or has none.  Opt-in (Sieve(decide_rows=...)); nothing
+ * else in the library calls it.
+ *
+ * Domains (host only).  An mh_domains holds, per column of one group, ascending by column, an
+ * interval [lo, lo + size) or an ascending list of values, and `rows`, the product of the sizes.
+ * Sizes and rows saturate at 2^64 - 1 (which then reads "at least"); an empty domain has size 0
+ * and makes rows 0.
+ *
+ * mh_domains_build reads them off ONE group's tape, in the conventions of mh_conjuncts_build /
+ * mh_guide_harvest: VAR imm0 = query column (< n_widths), CONST imm0 = query constant, the root a
+ * Bool conjunction whose AND leaves are flattened as the guide harvest flattens them.  group_cols
+ * are the group's columns (n_group_cols == 0, a ground group: no column and rows == 1, the one
+ * empty row; the generator then writes nothing and the tape decides).  A column's domain is a superset of
+ * the values it takes in any row that satisfies the tape, derived from the top-level conjuncts
+ * over its plain VAR node v only: the column width ([0, 2^w - 1]); v == c either way round; an OR
+ * tree whose every leaf is v == c_k for the same v (a list); unsigned comparisons of v with a
+ * constant either way round, their negations, and Or(ULT, ==) / Or(UGT, ==) (an interval: the
+ * reading MH_QUERY_REFUTED is decided by); Not(v == c) removes c from a list or trims an interval
+ * end, and is ignored inside an interval.  Everything is intersected; any other conjunct
+ * contributes nothing.  A null pointer, a column outside the widths, a constant outside the
+ * pool, an operand that is not an earlier node or a root that is not Bool is MH_E_INVALID.
+ *
+ * mh_domains_create builds the handle from the same arrays (mh_domains_desc's; col_width is
+ * indexed by column).  It validates them: columns ascending and inside the widths, list_off
+ * ascending from 0, a list's size its length and its values ascending and within the column's
+ * width, an interval without list values and with lo and lo + size - 1 within the width.       */
+enum { MH_DOMAIN_INTERVAL = 0, MH_DOMAIN_LIST = 1 };
+typedef struct mh_domains mh_domains;
+typedef struct {
+    const uint32_t* cols;        /* [n_cols] query columns, ascending                            */
+    const uint32_t* kind;        /* [n_cols] MH_DOMAIN_*                                         */
+    const uint64_t* size;        /* [n_cols] values in the domain, saturating                    */
+    const uint32_t* lo;          /* [n_cols][8] an interval's first value (zero for a list)      */
+    const uint32_t* list_off;    /* [n_cols + 1] ranges of list_vals, in values                  */
+    const uint32_t* list_vals;   /* x 8 limbs                                                    */
+    uint32_t n_cols;
+    uint32_t pad;
+    uint64_t rows;               /* product of the sizes, saturating                             */
+} mh_domains_desc;
+int32_t mh_domains_build(const mh_node* nodes, uint32_t n_nodes, const uint32_t* consts,
+                         uint32_t n_consts, const uint16_t* col_width, uint32_t n_widths,
+                         const uint32_t* group_cols, uint32_t n_group_cols, mh_domains** out);
+int32_t mh_domains_create(const uint32_t* cols, const uint32_t* kind, const uint64_t* size,
+                          const uint32_t* lo, const uint32_t* list_off, const uint32_t* list_vals,
+                          uint32_t n_cols, const uint16_t* col_width, uint32_t n_widths,
+                          mh_domains** out);
+/* *info points into the handle until mh_domains_free.                                            */
+int32_t mh_domains_info(const mh_domains* d, mh_domains_desc* info);
+int32_t mh_domains_free(mh_domains* d);
+/* The enumerating generator: buffer row first + r, r < count, gets global index g = global_base
+ * + r.  Domain column j (stride_0 = 1, stride_{j+1} = stride_j * size_j) gets digit d = (g /
+ * stride_j) mod size_j and the value list_j[d] or lo_j + d (a 256-bit sum); a column whose stride
+ * is 2^64 or more has digit 0.  Columns of the buffer outside the domain set are left untouched.
+ * global_base + count > rows, a row range beyond the buffer's capacity or a domain column beyond
+ * the buffer's columns is MH_E_INVALID, checked before any launch.  The per-column descriptors and
+ * list values go to the device once per domain set (on its first use), not per launch; a domain
+ * set is used with the buffers of one context.                                                   */
+int32_t mh_assign_enumerate(mh_assign* as, mh_domains* domains, uint64_t global_base,
+                            uint64_t first, uint64_t count);
+/* One enumeration window of a group in one call: mh_assign_enumerate of rows [0, count) then
+ * mh_run_rows of tape `tape` over them with index_base = global_base (one copy back, one sync),
+ * as mh_query_round is for a guided round.  first_hit / hit_count are [1], rows_out [n_cols][8]. */
+int32_t mh_query_enumerate(mh_ctx* ctx, const mh_tapeset* ts, mh_assign* as, mh_domains* domains,
+                           uint64_t global_base, uint64_t count, uint32_t tape, uint32_t mode,
+                           uint64_t* first_hit, uint64_t* hit_count, uint32_t n_cols,
+                           uint32_t* rows_out);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* ---- native-code path (no reference counterpart: replaces the interpreter for throughput runs)
  * mh_tapes_jit compiles every tape of the set that the JIT covers to gfx950 machine code -- one

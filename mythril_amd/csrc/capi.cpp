@@ -22,6 +22,7 @@
 #include "../../include/mythril_hip.h"
 #include "compile.h"
 #include "dev_isa.h"
+#include "domains.h"
 #include "jit.h"
 #include "kernels.h"
 #include "values_plan.h"
@@ -1625,6 +1626,94 @@ int32_t mh_query_round(mh_ctx* ctx, const mh_tapeset* ts, mh_assign* as, const m
     if (int32_t r = mh_assign_generate_guided(as, seed, global_base, 0, count, guide)) return r;
     return mh_run_rows(ctx, ts, tape_first, tape_count, as, 0, count, global_base, mode, first_hit,
                        hit_count, n_cols, rows_out);
+}
+
+// The device copy of a domain set: n KDomain descriptors, then the list values.  Made on the
+// set's first use with a context and kept in the handle (domains.h) until mh_domains_free, or
+// until the set is used with another context's buffer.
+static void domains_release(mh_domains* d) {
+    mh_ctx* ctx = static_cast<mh_ctx*>(d->dev_owner);
+    if (d->dev) {
+        settle(ctx);
+        (void)hipSetDevice(ctx->device);
+        (void)hipFree(d->dev);
+    }
+    d->dev = nullptr;
+    d->dev_owner = nullptr;
+    d->dev_release = nullptr;
+    ctx_unref(ctx);
+}
+
+static int32_t domains_upload(mh_domains* d, mh_ctx* ctx) {
+    if (d->dev && d->dev_owner == ctx) return MH_OK;
+    if (d->dev_release) d->dev_release(d);
+    const size_t n = d->cols.size();
+    std::vector<mh::KDomain> h(n);
+    for (size_t j = 0; j < n; ++j) {
+        mh::KDomain& k = h[j];
+        std::memset(&k, 0, sizeof k);
+        k.size = d->size[j];
+        k.col = d->cols[j];
+        k.kind = d->kind[j];
+        std::memcpy(k.lo, &d->lo[8 * j], sizeof k.lo);
+        k.list_off = d->list_off[j];
+    }
+    const size_t desc_bytes = n * sizeof(mh::KDomain);
+    const size_t val_bytes = d->list_vals.size() * sizeof(uint32_t);
+    void* dev = nullptr;
+    MH_HIP(hipMalloc(&dev, desc_bytes + std::max<size_t>(val_bytes, sizeof(uint32_t))));
+    hipError_t e = hipMemcpy(dev, h.data(), desc_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && val_bytes)
+        e = hipMemcpy(static_cast<char*>(dev) + desc_bytes, d->list_vals.data(), val_bytes,
+                      hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(dev);
+        return set_err(MH_E_DEVICE, std::string("domain upload: ") + hipGetErrorString(e));
+    }
+    d->dev = dev;
+    d->dev_owner = ctx;
+    d->dev_release = domains_release;
+    ++ctx->children;
+    return MH_OK;
+}
+
+int32_t mh_assign_enumerate(mh_assign* as, mh_domains* d, uint64_t global_base, uint64_t first,
+                            uint64_t count) {
+    // everything up to use_device() is host-only: a refused call has launched nothing
+    if (!as || !d) return set_err(MH_E_INVALID, "mh_assign_enumerate: null argument");
+    if (first > as->capacity || count > as->capacity - first)
+        return set_err(MH_E_INVALID, "mh_assign_enumerate: row range out of bounds");
+    if (global_base > d->rows || count > d->rows - global_base)
+        return set_err(MH_E_INVALID, "mh_assign_enumerate: global_base + count exceeds the rows");
+    for (uint32_t c : d->cols)
+        if (c >= as->n_vars)
+            return set_err(MH_E_INVALID, "mh_assign_enumerate: domain column " + std::to_string(c) +
+                                             " beyond the buffer's columns");
+    if (count == 0 || d->cols.empty()) return MH_OK;  // (a ground group: the one empty row)
+    if (int32_t r = use_device(as->ctx)) return r;
+    if (int32_t r = domains_upload(d, as->ctx)) return r;
+    const size_t n = d->cols.size();
+    const mh::KDomain* doms = static_cast<const mh::KDomain*>(d->dev);
+    const uint32_t* vals = reinterpret_cast<const uint32_t*>(doms + n);
+    MH_HIP(mh::launch_enumerate(as->d, as->stride, first, count, global_base, doms, (uint32_t)n,
+                                vals, as->ctx->stream));
+    return MH_OK;
+}
+
+int32_t mh_query_enumerate(mh_ctx* ctx, const mh_tapeset* ts, mh_assign* as, mh_domains* d,
+                           uint64_t global_base, uint64_t count, uint32_t tape, uint32_t mode,
+                           uint64_t* first_hit, uint64_t* hit_count, uint32_t n_cols,
+                           uint32_t* rows_out) {
+    if (!ctx || !as || as->ctx != ctx) return set_err(MH_E_INVALID, "null or foreign assignment buffer");
+    if (!d) return set_err(MH_E_INVALID, "mh_query_enumerate: null domains");
+    if (int32_t r = check_run_args(ctx, ts, tape, 1, as, 0, count, mode)) return r;
+    if (n_cols && (!rows_out || n_cols > as->n_vars))
+        return set_err(MH_E_INVALID, "mh_query_enumerate: rows_out null or n_cols beyond the buffer's columns");
+    if (int32_t r = refuse_tables(ts)) return r;
+    // the generator, the run and the copy queue back to back on the ctx stream: one host sync
+    if (int32_t r = mh_assign_enumerate(as, d, global_base, 0, count)) return r;
+    return mh_run_rows(ctx, ts, tape, 1, as, 0, count, global_base, mode, first_hit, hit_count,
+                       n_cols, rows_out);
 }
 
 int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jobs) {

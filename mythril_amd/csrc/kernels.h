@@ -81,6 +81,22 @@ struct KGuide {
 hipError_t launch_generate_guided(uint32_t* assign, uint64_t stride, uint64_t first,
                                   uint64_t count, uint64_t seed, uint64_t base, const KGuide& g,
                                   hipStream_t stream);
+// One domain column of an enumeration (mh_assign_enumerate; enumerate.hip), 64 bytes, on the
+// device once per domain set; a list's values are 8-limb entries of the set's value block.
+struct KDomain {
+    uint64_t size;      // values in the domain (> 0 in any launch)
+    uint32_t col;       // the buffer column written
+    uint32_t kind;      // MH_DOMAIN_*
+    uint32_t lo[8];     // an interval's first value
+    uint32_t list_off;  // a list's first entry in the value block
+    uint32_t pad[3];
+};
+static_assert(sizeof(KDomain) == 64, "KDomain is packed by words (capi.cpp)");
+// rows [first, first + count) of the buffer: the cross product's rows base.. in order; the caller
+// has checked every column and the row range against the buffer
+hipError_t launch_enumerate(uint32_t* assign, uint64_t stride, uint64_t first, uint64_t count,
+                            uint64_t base, const KDomain* doms, uint32_t n_doms,
+                            const uint32_t* list_vals, hipStream_t stream);
 // A batched round (mh_query_round_many; the tables are batch_plan.h's, on the device, read only).
 // Interpreter: workgroup i of the launch runs blocks[i] = {segment, row block, tape slice, slices}
 // with segs[segment]; `variant` serves every segment of the launch.  A round's launches are

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/mythril_hip.h"
+#include "bound_read.h"
 
 int32_t mh_detail_set_err(int32_t code, const char* msg);  // capi.cpp
 
@@ -1026,25 +1027,8 @@ bool may_define(const std::vector<mh_node>& tape, const std::vector<uint8_t>& ha
     return false;
 }
 
-struct Cmp {
-    uint8_t op;
-    uint32_t t, c;  // tape nodes: the term, the constant
-};
-
-// t op c for a comparison node of a bit-vector term t with a constant c (either side; a constant on
-// the left mirrors the comparison)
-bool cmp_of_plain(const std::vector<mh_node>& tape, uint32_t n, Cmp& out) {
-    const mh_node& x = tape[n];
-    uint8_t op = x.op;
-    if (op != EQ && !(op >= BVULT && op <= MH_OP_BVUGE)) return false;
-    const bool ca = tape[x.a].op == CONST, cb = tape[x.b].op == CONST;
-    if (ca == cb || tape[x.a].width == 0) return false;
-    if (ca)
-        op = op == BVULT ? MH_OP_BVUGT : op == MH_OP_BVULE ? MH_OP_BVUGE
-           : op == MH_OP_BVUGT ? BVULT : op == MH_OP_BVUGE ? MH_OP_BVULE : op;
-    out = {op, ca ? x.b : x.a, ca ? x.a : x.b};
-    return true;
-}
+// t op c read off a comparison node (bound_read.h: shared with the domain analysis, domains.cpp)
+using mh::bound::Cmp;
 
 // A conjunction that contradicts itself syntactically (sound, not complete): a FALSE conjunct, a
 // conjunct and its negation, or one term pinned by its conjuncts -- t == c, t != c, unsigned
@@ -1104,20 +1088,6 @@ bool refuted(const Query& Q, const std::vector<uint32_t>& conj) {
         }
         return S.ranges[S.range_of[t]];
     };
-    // smt.py's ULE / UGE (bitvec_helper.py: Or(ULT(a, b), a == b)) read as BVULE / BVUGE
-    auto cmp_of = [&](uint32_t n, Cmp& out) -> bool {
-        const mh_node& x = tape[n];
-        if (x.op == MH_OP_OR) {
-            Cmp p, e;
-            if (!cmp_of_plain(tape, x.a, p) || !cmp_of_plain(tape, x.b, e)) return false;
-            if (p.op == EQ) std::swap(p, e);
-            if (e.op != EQ || p.t != e.t || p.c != e.c) return false;
-            if (p.op != BVULT && p.op != MH_OP_BVUGT) return false;
-            out = {(uint8_t)(p.op == BVULT ? MH_OP_BVULE : MH_OP_BVUGE), p.t, p.c};
-            return true;
-        }
-        return cmp_of_plain(tape, n, out);
-    };
     for (uint32_t cj : conj) {
         const mh_node& x0 = tape[cj];
         if (x0.op == FALSE_) return true;
@@ -1129,13 +1099,11 @@ bool refuted(const Query& Q, const std::vector<uint32_t>& conj) {
             n = x0.a;
         }
         Cmp k;
-        if (!cmp_of(n, k)) continue;
+        if (!mh::bound::cmp_of(tape.data(), n, k)) continue;
         uint8_t op = k.op;
         const uint32_t t = k.t;
         const Big* c = &Q.qpool[tape[k.c].imm0];
-        if (neg)  // not (t < c) is t >= c, ...; not (t == c) is t != c
-            op = op == BVULT ? MH_OP_BVUGE : op == MH_OP_BVULE ? MH_OP_BVUGT
-               : op == MH_OP_BVUGT ? MH_OP_BVULE : op == MH_OP_BVUGE ? BVULT : op;
+        if (neg) op = mh::bound::negated(op);  // not (t < c) is t >= c, ...; not (t == c) is t != c
         RefuteScratch::Range& r = range(t);
         if (op == EQ && neg) {
             r.ne.push_back(k.c);

@@ -63,6 +63,11 @@ _config = {
     "certify_resident": None,  # sieve_model's own certification goes through the sieve's
                                # resident Certifier (certify.py); None: SIEVE_CERTIFY_RESIDENT=1
                                # turns it on, off by default
+    "decide": None,     # what a query the sieve decided UNSAT (Sieve.last_unsat; needs the sieve
+                        # option decide_rows) becomes: False / off -- a miss like any other;
+                        # True -- UnsatError without the fallback; "audit" -- the fallback is
+                        # still asked and a model it returns is counted as a dispute.  None: the
+                        # SIEVE_DECIDE environment variable ("1" / "audit"), off by default
 }
 
 
@@ -75,12 +80,18 @@ def configure(*, fallback: Optional[Callable] = None, verify: Optional[Callable]
               to_terms: Optional[Callable] = None, enabled: Optional[bool] = None,
               log_writer: Optional[Callable] = None, fallback_logs: Optional[bool] = None,
               certify: Optional[bool] = None, certify_resident: Optional[bool] = None,
-              **sieve_kwargs) -> None:
+              decide=None, **sieve_kwargs) -> None:
     """Set the fallback solver, the witness verifier, the term importer and sieve options.
     ``certify=True`` (or SIEVE_CERTIFY=1) certifies every witness against the original
     constraints on the device before it is returned or verified (certify.py);
     ``certify_resident=True`` (or SIEVE_CERTIFY_RESIDENT=1) does so through the sieve's resident
-    Certifier, which keeps a path's compiled constraints between queries."""
+    Certifier, which keeps a path's compiled constraints between queries.
+    ``decide`` (or SIEVE_DECIDE) says what a query the sieve decided UNSAT by enumeration becomes
+    (decide_mode); the decisions themselves are switched on by the sieve option ``decide_rows``."""
+    if decide is not None:
+        if decide not in (True, False, "audit"):
+            raise ValueError("decide must be True, False or 'audit'")
+        _config["decide"] = decide
     if certify is not None:
         _config["certify"] = bool(certify)
     if certify_resident is not None:
@@ -120,6 +131,19 @@ def certify_resident_on() -> bool:
     return os.environ.get("SIEVE_CERTIFY_RESIDENT", "") == "1" if c is None else c
 
 
+def decide_mode():
+    """False (the default: a decided-UNSAT query is a miss like any other), True (it raises
+    UnsatError without the fallback) or "audit" (the fallback is still asked, and a model it
+    returns is a dispute): configure(decide=...) when set, else SIEVE_DECIDE ("1" / "audit")."""
+    import os
+
+    d = _config["decide"]
+    if d is None:
+        e = os.environ.get("SIEVE_DECIDE", "")
+        d = True if e == "1" else "audit" if e == "audit" else False
+    return d
+
+
 def _takes_timeout(fn) -> bool:
     try:
         ps = inspect.signature(fn).parameters.values()
@@ -140,7 +164,7 @@ def reset() -> None:
     """Back to defaults (tests, plugin stop)."""
     _config.update(fallback=None, verify=None, to_terms=None, log_writer=None,
                    fallback_logs=False, sieve_kwargs={}, enabled=True, certify=None,
-                   certify_resident=None)
+                   certify_resident=None, decide=None)
     close_sieve()
     clear_prefetched()
     get_model.cache_clear()
@@ -213,6 +237,22 @@ def _log_query(constraints, minimize, maximize) -> None:
         log.debug("--solver-log write failed: %s", e)
 
 
+def _query_text(constraints) -> str:
+    """The query as SMT-LIB2 for a log message (a disputed decision), best effort."""
+    from . import smt
+
+    try:
+        if all(isinstance(c, smt.Bool) for c in constraints):
+            from .smtlib import to_smtlib
+
+            return to_smtlib(constraints, (), ())
+        if _config["log_writer"] is not None:
+            return _config["log_writer"](constraints, (), ())
+    except Exception:  # noqa: BLE001 - a message must not change the answer
+        pass
+    return repr(constraints)
+
+
 def _terms(constraints):
     """(smt.Context, [Bool]) for the constraints: ours as they are, foreign ones imported."""
     from . import smt
@@ -252,7 +292,7 @@ def _parked_verdicts() -> dict:
 
 def clear_prefetched() -> None:
     """Drop this thread's parked answers (configure, reset, forget_witnesses do)."""
-    for name in ("parked", "parked_verdicts"):
+    for name in ("parked", "parked_verdicts", "parked_unsat"):
         t = getattr(_tls, name, None)
         if t:
             t.clear()
@@ -306,6 +346,12 @@ def prefetch(queries) -> int:
         log.debug("prefetch left to the ordinary path: %s", e)
         return 0
     verdicts = _parked_verdicts()
+    unsat = getattr(_tls, "parked_unsat", None)
+    if unsat is None:
+        unsat = _tls.parked_unsat = set()
+    for (_, key), rec in zip(items, s.last_many):  # the parked misses that were decisions
+        if rec["error"] is None:
+            (unsat.add if rec.get("unsat") else unsat.discard)(key)
     for key, entry in fresh:
         table[key] = entry
         table.move_to_end(key)
@@ -351,6 +397,7 @@ def sieve_model(constraints, timeout_ms: Optional[float] = None):
     stats = SolverStatistics()
     t0 = time.perf_counter()
     _tls.miss_key = None
+    _tls.decided_unsat = False  # this call's miss was a decision (get_model reads it)
     try:
         s = sieve()  # first: an unusable device skips the term import
         ctx, terms = _terms(constraints)
@@ -367,8 +414,14 @@ def sieve_model(constraints, timeout_ms: Optional[float] = None):
             # answered by prefetch(): no round here; a miss leaves the sieve as solve() would
             # have, so the fallback's model of it is learnt
             _, w, s.last_miss, s.last_rounds = entry
+            pu = getattr(_tls, "parked_unsat", None)
+            unsat = bool(pu) and key in pu
+            if unsat:
+                pu.discard(key)
         else:
             w = s.solve(ctx.b, [t.node for t in terms], key=key, budget_s=budget)
+            unsat = bool(getattr(s, "last_unsat", False))
+        _tls.decided_unsat = w is None and unsat
     except Exception as e:  # fail closed: any problem means "ask the fallback"
         from .lower import LoweringUnsupported
         from .native import Unsupported
@@ -460,13 +513,25 @@ def get_model(constraints, minimize=(), maximize=(), enforce_execution_time=True
             if args.solver_log:
                 _log_query(constraints, minimize, maximize)
             return m
-    if args.solver_log and (fallback is None or not _config["fallback_logs"]):
+    # a miss that was a decision (Sieve.last_unsat: an eligible group enumerated to its end, or
+    # an eligible query the host refuted), under decide=True / "audit"
+    mode = decide_mode() if getattr(_tls, "decided_unsat", False) else False
+    _tls.decided_unsat = False
+    if mode:
+        stats.sieve_unsat += 1
+    if args.solver_log and (fallback is None or not _config["fallback_logs"] or mode is True):
         _log_query(constraints, minimize, maximize)
+    if mode is True:  # the sieve's own UNSAT: the fallback is not asked
+        raise UnsatError
     if fallback is None:
         log.debug("sieve found no witness and no fallback solver is configured")
         raise UnsatError
     # the fallback (the reference's get_model) counts itself through stat_smt_query
     model = fallback(tuple(constraints), minimize, maximize, enforce_execution_time)
+    if mode == "audit" and model is not None:
+        stats.sieve_unsat_disputed += 1
+        log.warning("sieve decided UNSAT, the fallback found a model: %s",
+                    _query_text(constraints))
     learn_from_fallback(model)
     return model
 

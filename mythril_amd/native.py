@@ -143,6 +143,15 @@ SIGNATURES = {
     "mh_repair_select": (C.c_int32, [_vp, C.c_uint32, C.c_uint64, _vp, _u32p]),
     "mh_repair_mutate": (C.c_int32, [_vp, _vp, _vp, _vp, _u32p, _u32p, _u32p, C.c_uint32,
                                      C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "mh_domains_build": (C.c_int32, [_vp, C.c_uint32, _u32p, C.c_uint32, C.POINTER(C.c_uint16),
+                                     C.c_uint32, _u32p, C.c_uint32, C.POINTER(_vp)]),
+    "mh_domains_create": (C.c_int32, [_u32p, _u32p, _u64p, _u32p, _u32p, _u32p, C.c_uint32,
+                                      C.POINTER(C.c_uint16), C.c_uint32, C.POINTER(_vp)]),
+    "mh_domains_info": (C.c_int32, [_vp, _vp]),
+    "mh_domains_free": (C.c_int32, [_vp]),
+    "mh_assign_enumerate": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "mh_query_enumerate": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32,
+                                       C.c_uint32, _u64p, _u64p, C.c_uint32, _u32p]),
 }
 
 # mh_smt_record / mh_smt_result (include/mythril_hip.h)
@@ -591,6 +600,15 @@ class CompiledQuery:
                               None if ko == 0xFFFFFFFF else keys[ko])
                              for no, nl, so, sl, w, k, ko, _ in cols.tolist()]
         return self._columns
+
+    def column_kinds(self) -> List[int]:
+        """MH_COL_* per column, without decoding the columns."""
+        return self._raw[1]["kind"].tolist()
+
+    def has_keccak_table(self) -> bool:
+        """Whether the lowering made an MH_TABLE_KECCAK table, without decoding the tables."""
+        return bool((np.frombuffer(self._raw[3], dtype=QUERY_TABLE_DTYPE)["kind"]
+                     == TABLE_KECCAK).any())
 
     @property
     def tables(self) -> List[tuple]:
@@ -1072,6 +1090,13 @@ class Assignments:
         _check(self.ctx.lib.mh_assign_generate_guided(self.h, seed, global_base, first, count,
                                                       C.byref(g)))
 
+    def enumerate(self, domains: "Domains", global_base: int = 0, first: int = 0,
+                  count: Optional[int] = None) -> None:
+        """Rows [first, first+count) get rows global_base.. of the domains' cross product
+        (mh_assign_enumerate; decide.enumerate_rows restates it)."""
+        count = self.capacity - first if count is None else count
+        _check(self.ctx.lib.mh_assign_enumerate(self.h, domains.h, global_base, first, count))
+
     def close(self) -> None:
         if self.h:
             self.ctx.lib.mh_assign_destroy(self.h)
@@ -1360,6 +1385,111 @@ class ConjunctPlan:
         for i, leaf in enumerate(self.leaf.tolist()):
             first.setdefault(leaf, i)
         return np.array([first.get(int(t), NO_CONJUNCT) for t in set_conj], dtype=np.uint32)
+
+
+DOMAIN_INTERVAL = 0  # MH_DOMAIN_*
+DOMAIN_LIST = 1
+ROWS_SATURATED = 0xFFFFFFFFFFFFFFFF  # a domain size / row count of 2^64 - 1 reads "at least"
+
+
+class DomainsDesc(C.Structure):
+    """mh_domains_desc (include/mythril_hip.h)."""
+
+    _fields_ = [("cols", _u32p), ("kind", _u32p), ("size", _u64p), ("lo", _u32p),
+                ("list_off", _u32p), ("list_vals", _u32p), ("n_cols", C.c_uint32),
+                ("pad", C.c_uint32), ("rows", C.c_uint64)]
+
+
+class Domains:
+    """mh_domains: per group column (``cols`` ascending) an interval (``lo``, ``size``) or an
+    ascending value list (``lists``), and ``rows``, the product of the sizes (saturating).  Made
+    by ``domains_build`` from a group's tape or ``domains_create`` from plain values; the handle
+    stays open for the enumerating generator (Assignments.enumerate, query_enumerate) until
+    close()."""
+
+    def __init__(self, lib, h: C.c_void_p):
+        self.lib, self.h = lib, h
+        d = DomainsDesc()
+        try:
+            _check(lib.mh_domains_info(h, C.byref(d)))
+            n = int(d.n_cols)
+
+            def arr(p, k):  # (an empty vector's pointer may be null)
+                return np.ctypeslib.as_array(p, shape=(k,)).copy() if k else np.zeros(0, p._type_)
+
+            self.cols = arr(d.cols, n).tolist()
+            self.kind = arr(d.kind, n).tolist()
+            self.size = arr(d.size, n).tolist()
+            self.lo = _ints(arr(d.lo, 8 * n).reshape(n, 8))
+            off = arr(d.list_off, n + 1).tolist()
+            vals = _ints(arr(d.list_vals, 8 * off[-1]).reshape(-1, 8))
+            self.lists = [vals[off[j]:off[j + 1]] for j in range(n)]
+            self.rows = int(d.rows)
+        except BaseException:
+            self.close()
+            raise
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.mh_domains_free(self.h)
+            self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def domains_build(nodes: np.ndarray, consts: np.ndarray, widths: Sequence[int],
+                  group_cols: Sequence[int] = ()) -> Domains:
+    """The domains of the columns ``group_cols`` of one group's tape (mh_domains_build; host
+    only).  No column: a ground group, whose product is the one empty row."""
+    lib = load()
+    nodes = np.ascontiguousarray(nodes, dtype=NODE_DTYPE)
+    consts = np.ascontiguousarray(consts, dtype=np.uint32).reshape(-1, 8)
+    w = np.ascontiguousarray(widths, dtype=np.uint16)
+    gc = np.ascontiguousarray(list(group_cols), dtype=np.uint32)
+    h = C.c_void_p()
+    _check(lib.mh_domains_build(nodes.ctypes.data, len(nodes), _ptr(consts), len(consts),
+                                _ptr(w, C.c_uint16), len(w), _ptr(gc), len(gc), C.byref(h)))
+    return Domains(lib, h)
+
+
+def domains_create(cols: Sequence[int], kinds: Sequence[int], sizes: Sequence[int],
+                   los: Sequence[int], lists: Sequence[Sequence[int]],
+                   widths: Sequence[int]) -> Domains:
+    """A domain set from plain values (mh_domains_create validates them): per column its kind,
+    size, an interval's ``lo`` and a list's values; ``widths`` by query column."""
+    lib = load()
+    n = len(cols)
+    off = np.zeros(n + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(x) for x in lists])
+    vals = _limb_rows([v for x in lists for v in x] or [0])
+    h = C.c_void_p()
+    _check(lib.mh_domains_create(
+        _ptr(np.ascontiguousarray(cols, dtype=np.uint32)),
+        _ptr(np.ascontiguousarray(kinds, dtype=np.uint32)),
+        _ptr(np.ascontiguousarray(sizes, dtype=np.uint64), C.c_uint64),
+        _ptr(_limb_rows(list(los) or [0])), _ptr(off), _ptr(vals), n,
+        _ptr(np.ascontiguousarray(widths, dtype=np.uint16), C.c_uint16), len(widths),
+        C.byref(h)))
+    return Domains(lib, h)
+
+
+def query_enumerate(ctx: Context, tapes: CompiledTapes, assign: "Assignments", domains: Domains,
+                    global_base: int, count: int, n_cols: int, *, tape: int = 0,
+                    mode: int = MODE_FIRST_HIT):
+    """One enumeration window (mh_query_enumerate): rows [0, count) of `assign` get the cross
+    product's rows global_base.., then tape `tape` runs over them with index_base = global_base.
+    Returns (first_hit, hit_count, rows) as query_round does, for the one tape."""
+    fh = np.zeros(1, dtype=np.uint64)
+    hc = np.zeros(1, dtype=np.uint64)
+    rows = np.zeros((1, max(n_cols, 1), 8), dtype=np.uint32)
+    _check(ctx.lib.mh_query_enumerate(ctx.h, tapes.h, assign.h, domains.h, global_base, count,
+                                      tape, mode, _ptr(fh, C.c_uint64), _ptr(hc, C.c_uint64),
+                                      n_cols, _ptr(rows)))
+    return fh, hc, rows[:, :n_cols]
 
 
 class Repair:

@@ -32,7 +32,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import native
+from . import decide, native
 from .lower import (Column, KeccakMap, LoweringUnsupported, Schema, cell_name, lower_query,
                     node_columns)
 from .tape import NODE_DTYPE, Op, Tape, TapeBuilder, TapeError, TapeSet
@@ -421,14 +421,17 @@ class _Staged:
     lowering, the parent witness it was harvested under, the kept guide and the compiled tapes."""
 
     __slots__ = ("b", "key", "keccak_reads", "base_schema", "qno", "host", "col_index", "parent",
-                 "parent_len", "guide", "ct", "t1")
+                 "parent_len", "guide", "ct", "t1", "decide")
 
     def __init__(self, b, key, keccak_reads, base_schema, qno, host, col_index, parent,
-                 parent_len, guide, ct, t1):
+                 parent_len, guide, ct, t1, decide=None):
         self.b, self.key, self.keccak_reads, self.base_schema = b, key, keccak_reads, base_schema
         self.qno, self.host, self.col_index = qno, host, col_index
         self.parent, self.parent_len, self.guide, self.ct, self.t1 = (parent, parent_len, guide,
                                                                       ct, t1)
+        # (keccak reads?, keccak table?, column kinds) of a natively built query, for the
+        # decision step's eligibility; None: never decided (the Python host stages)
+        self.decide = decide
 
     def close(self) -> None:  # a staged query whose rounds never ran
         self.ct.close()
@@ -442,7 +445,8 @@ class Sieve:
                  seed: int = 0x5EED5EED, budget_s: float = 0.25, first_rows: Optional[int] = None,
                  native_query: bool = True, second_round: Optional[str] = None,
                  keccak_second_chance: Optional[bool] = None, repair_rounds: int = 0,
-                 repair_elites: Optional[int] = None, repair_children: Optional[int] = None):
+                 repair_elites: Optional[int] = None, repair_children: Optional[int] = None,
+                 decide_rows: int = 0):
         self.ctx = native.Context(device)
         # host stages by the native query compiler (csrc/query.cpp); False: the Python stages
         # (lower.py, buckets, local_tapeset) it is checked against (tests/test_query_native.py)
@@ -537,6 +541,20 @@ class Sieve:
         # rows' best are no nearer, and K is fixed -- 0.840 -> 0.862 on the same workload
         self.repair_score_rows = min(1 << 16, max(1, int(
             os.environ.get("SIEVE_REPAIR_SCORE_ROWS", "4096"))))
+        # decision by enumeration (Sieve._decide): after the rounds and repair, a group
+        # still unsolved whose columns all have provable finite domains (native.domains_build)
+        # with at most this many rows in their cross product is enumerated in order and decided
+        # exactly -- its smallest row, or none, which makes the query UNSAT (last_unsat).  0 (the
+        # default) runs none of it.  SIEVE_DECIDE_ROWS overrides.  (Capped far below the 2^64 - 1
+        # at which a row count only reads "at least".)
+        self.decide_rows = min(1 << 40, max(0, int(os.environ.get("SIEVE_DECIDE_ROWS",
+                                                                   decide_rows))))
+        # the last query was decided UNSAT: an eligible group has no row, or the host refuted an
+        # eligible query.  Cleared per query; solve() still returns None.
+        self.last_unsat = False
+        self._refuted_unsat: set = set()  # numbers of refuted queries that were eligible
+        self._decide_info = None          # the last native host stage's (keccak table?, kinds)
+        self._refuted_eligible = False
         self.repairer = None                                  # native.Repair, made on first use
         self.assign2: Optional[native.Assignments] = None     # the children's buffer
         # solve_many: first-round buffers (first_rows rows) by column capacity, kept between
@@ -784,8 +802,14 @@ class Sieve:
             st.add("lower", time.perf_counter() - t0)
             return None
         st.add("lower", time.perf_counter() - t0)
+        if self.decide_rows > 0:  # what eligibility reads (decide.eligible), for _stage
+            self._decide_info = (keccak_reads, cq.has_keccak_table(), cq.column_kinds())
         if cq.flags & native.QUERY_REFUTED:
             st.extra["refuted"] = st.extra.get("refuted", 0) + 1
+            # the refuted conjunction is the lowered one: it stands for the caller's only when
+            # every group is eligible (none of the query's columns or tapes touches keccak)
+            self._refuted_eligible = self.decide_rows > 0 and decide.eligible(
+                *self._decide_info, range(len(cq.names)), cq.nodes)
             return REFUTED
         columns = cq.names
         defs = []
@@ -865,6 +889,7 @@ class Sieve:
         self.stats.queries += 1
         self.last_rounds = {}
         self.last_miss = None
+        self.last_unsat = False
         if budget <= 0:
             self.stats.misses += 1
             return None
@@ -878,8 +903,13 @@ class Sieve:
         second chance and the accounting of the answer.  ``first``: its first round's results when
         a batched round (solve_many) has run it already."""
         st = self.stats
+        self.last_unsat = False
         if staged is REFUTED:
             w, schema, kec = None, REFUTED, False
+            if qno in self._refuted_unsat:
+                self._refuted_unsat.discard(qno)
+                self.last_unsat = True
+                st.extra["decided_unsat"] = st.extra.get("decided_unsat", 0) + 1
         else:
             w, schema, kec = self._rounds(staged, budget, t0, first)
         schema2 = None
@@ -937,8 +967,8 @@ class Sieve:
         given as a list), with the first round of
         every query that needs one run in one device submission (native.query_round_many)
         instead of one submission each.  Returns a witness or None per query; ``last_many`` has,
-        per query, ``miss`` (what last_miss would have been), ``rounds`` (last_rounds) and
-        ``error`` (the exception an unsupported query raises from solve(), reported here instead:
+        per query, ``miss`` (what last_miss would have been), ``rounds`` (last_rounds), ``unsat``
+        (True for a query decided UNSAT, last_unsat; absent otherwise) and ``error`` (the exception an unsupported query raises from solve(), reported here instead:
         it does not fail the list).
 
         On Sieves created alike, the witnesses, their ``index`` and ``rounds``, the stats counters
@@ -1050,6 +1080,8 @@ class Sieve:
                     except Exception as e:  # noqa: BLE001
                         rec[q]["error"] = e
                     rec[q]["miss"], rec[q]["rounds"] = self.last_miss, self.last_rounds
+                    if self.last_unsat:  # (only ever with decide_rows set)
+                        rec[q]["unsat"] = True
             finally:
                 for s in staged.values():  # an interrupted batch: nothing stays open
                     if s is not REFUTED:
@@ -1057,6 +1089,7 @@ class Sieve:
             i = j
         self.last_rounds = {}
         self.last_miss = None
+        self.last_unsat = False
         return out
 
     def _guide_session(self, keccak_reads: bool) -> "native.GuideSession":
@@ -1135,11 +1168,17 @@ class Sieve:
         (or its close()) releases them."""
         st = self.stats
         th = time.perf_counter()
+        self._decide_info = None
+        self._refuted_eligible = False
         host = self._host_native(b, roots, keccak_reads) if self.native_query else None
         if host is REFUTED:  # no witness exists: no device round (the fallback still runs)
             self.stats.host_s += time.perf_counter() - th
+            if self._refuted_eligible:
+                self._refuted_unsat.add(qno)
             return REFUTED
+        dinfo = self._decide_info  # (a query that takes the Python stages is never decided)
         if host is None:
+            dinfo = None
             host = self._host_python(b, roots, keccak_reads)
         columns, widths, schema, root_nodes, ts, group_cols, defs, root_ends = host
         t_t = time.perf_counter()
@@ -1180,7 +1219,7 @@ class Sieve:
             guide.close()
             raise
         return _Staged(b, key, keccak_reads, base_schema, qno, host, col_index, parent, parent_len,
-                       guide, ct, t1)
+                       guide, ct, t1, dinfo)
 
     def _rounds(self, s: "_Staged", budget: float, t0: float, first=None):
         """The rounds of a staged query: (witness or None, schema, whether a group left unsolved
@@ -1321,6 +1360,28 @@ class Sieve:
                         st.add("definitions", time.perf_counter() - td)
                     return (Witness(schema, values, first_index, self.last_rounds["rounds"],
                                     repaired=True), schema, False)
+            if self.decide_rows > 0 and s.decide is not None and not all(solved):
+                if assign is None:
+                    assign = self._buffer(len(columns))
+                unsat, hit = self._decide(s.decide, ts, ct, assign, columns, widths, group_cols,
+                                          solved, values, budget, t0)
+                if unsat:  # an eligible group has no row: no witness, and no second chance
+                    self.last_unsat = True
+                    st.extra["decided_unsat"] = st.extra.get("decided_unsat", 0) + 1
+                    return None, schema, False
+                if hit is not None:
+                    first_index = hit if first_index is None else min(first_index, hit)
+                if all(solved):
+                    for c in columns:
+                        values.setdefault(c, 0)
+                    if defs:
+                        td = time.perf_counter()
+                        got = self.eval_definitions(b, defs, columns, values)
+                        for (c, _), v in zip(defs, got):
+                            values[c] = v
+                        st.add("definitions", time.perf_counter() - td)
+                    return (Witness(schema, values, first_index,
+                                    self.last_rounds.get("rounds", 0)), schema, False)
             kec = any(not solved[g] and _reads_keccak(ts.tapes[g].nodes)
                       for g in range(len(solved)))
             return None, schema, kec
@@ -1331,6 +1392,65 @@ class Sieve:
                 inc_guide.close()
             # (a batched query's stage ended before the other queries' stages and the batch)
             self.stats.device_s += time.perf_counter() - (t1 if first is None else t_c)
+
+    def _decide(self, info, ts, ct, assign, columns, widths, group_cols, solved, values, budget,
+                t0):
+        """The decision step (DESIGN §6 "Decision by enumeration"), after the rounds and repair:
+        every group still unsolved that is eligible (decide.eligible: UNSAT of the lowered group
+        implies UNSAT of the caller's constraints) and whose domains' cross product has at most
+        decide_rows rows is enumerated in order, in windows of the sieve's buffer
+        (mh_query_enumerate, FIRST_HIT), up to the first window with a hit.  A hit fills
+        `values` / `solved` as a round's does.  Returns (whether some group was found empty --
+        no rows at all, or enumerated to the end without a hit -- which makes the query UNSAT,
+        the smallest hit index or None).  A group whose enumeration the budget cuts short stays
+        undecided, never empty."""
+        st = self.stats
+        ex = st.extra
+        first_hit = None
+        consts = ts.pool.to_array()
+        for g in range(len(solved)):
+            if solved[g]:  # (a ground group's product is the one empty row: its tape decides)
+                continue
+            nodes = ts.tapes[g].nodes
+            if not decide.eligible(*info, group_cols[g], nodes):
+                ex["decide_ineligible"] = ex.get("decide_ineligible", 0) + 1
+                continue
+            td = time.perf_counter()
+            dom = native.domains_build(nodes, consts, widths, group_cols[g])
+            try:
+                if dom.rows > self.decide_rows:
+                    ex["decide_too_large"] = ex.get("decide_too_large", 0) + 1
+                    continue
+                window = assign.capacity
+                base, hit, row = 0, None, None
+                while base < dom.rows:
+                    if time.perf_counter() - t0 > budget:
+                        break
+                    n = min(window, dom.rows - base)
+                    fh, _, wrows = native.query_enumerate(self.ctx, ct, assign, dom, base, n,
+                                                          len(columns), tape=g,
+                                                          mode=native.MODE_FIRST_HIT)
+                    ex["decide_rows"] = ex.get("decide_rows", 0) + n
+                    st.rows += n
+                    base += n
+                    if int(fh[0]) != native.NO_HIT:
+                        hit, row = int(fh[0]), wrows[0]
+                        break
+                if hit is not None:
+                    raw = np.ascontiguousarray(row, dtype="<u4").tobytes()
+                    for c in group_cols[g]:
+                        values[columns[c]] = int.from_bytes(raw[32 * c:32 * c + 32], "little")
+                    solved[g] = True
+                    first_hit = hit if first_hit is None else min(first_hit, hit)
+                    ex["decided_sat"] = ex.get("decided_sat", 0) + 1
+                elif base >= dom.rows:  # the whole product (or an empty one) holds no model
+                    return True, first_hit
+                else:
+                    ex["decide_budget"] = ex.get("decide_budget", 0) + 1
+            finally:
+                dom.close()
+                st.add("decide", time.perf_counter() - td)
+        return False, first_hit
 
     def _repair(self, root_nodes, ts, ct, guide, assign, n_rows, columns, group_cols, solved,
                 values, base, budget, t0):

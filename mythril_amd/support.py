@@ -96,7 +96,10 @@ except Exception:  # z3 / mythril absent: standalone mirrors
     time_handler = _TimeHandler()
 
 _SIEVE_FIELDS = ("sieve_hits", "sieve_misses", "sieve_unsupported", "sieve_errors",
-                 "sieve_rejected", "sieve_uncertified")
+                 "sieve_rejected", "sieve_uncertified",
+                 # queries the sieve decided UNSAT by enumeration (frontend decide=True / "audit"),
+                 # and those of them the fallback then found a model for ("audit")
+                 "sieve_unsat", "sieve_unsat_disputed")
 
 
 class _Stats:

@@ -152,6 +152,11 @@ int32_t mh_tapes_compile_wait(mh_ctx* ctx, mh_tapeset** out,
                               double* compile_s /* the compile's own seconds, or NULL */);
 int32_t mh_tapes_destroy(mh_tapeset* ts);
 int32_t mh_tapes_info(const mh_tapeset* ts, mh_tape_info* info /* [n_tapes] */, uint32_t n_tapes);
+/* Spill slots per tape: 0 for a tape whose live values fit the interpreter's registers; a tape
+ * with more (n_regs 15, features bit 5) keeps that many 256-bit slots per row in device memory
+ * the ctx owns, and runs in a kernel of its own.  A run whose spill areas would exceed 256 MiB is
+ * MH_E_UNSUPPORTED, refused before anything is queued.                                           */
+int32_t mh_tapes_spills(const mh_tapeset* ts, uint32_t* out /* [n_tapes] */, uint32_t n_tapes);
 
 /* ---- assignments ----------------------------------------------------------------------------- */
 /* Layout in HBM: column v, limb k (0 = least significant) of assignment i is word

@@ -15,8 +15,11 @@ constexpr uint32_t kRowsPerBlock = 64;   // one-wave workgroups: the short-run s
 constexpr uint32_t kMaxRows = 4096;      // a job's rows at most (sieve_kernels.hip kShortRows)
 constexpr uint32_t kGenRowsPerBlock = 64;    // LDS generator forms (generate.hip kLdsRows)
 constexpr uint32_t kGenRowsPerBlockMem = 256;  // in-memory form (generate.hip kBlock)
-constexpr uint32_t kInterpVariants = 12;  // NR class x feature class; table variants never batch
-constexpr uint32_t kClasses = 3;
+// NR class x feature class, then a fourth class of four: the table variants 12..14, which never
+// batch (a round's tapes hold no lookup), and the spill variant 15 (kernels.h kSpillVariant), whose
+// segments share one spill region indexed by the launch's workgroup
+constexpr uint32_t kInterpVariants = 16;
+constexpr uint32_t kClasses = 4;
 constexpr uint32_t kForms = 3;
 constexpr uint32_t kMinBlocks = 256;     // launch_block's target: a workgroup per CU
 

@@ -95,6 +95,12 @@ struct mh_ctx {
     void* h_batch = nullptr;
     void* d_batch = nullptr;
     size_t h_batch_bytes = 0, d_batch_bytes = 0;
+    // the spill areas of the launches that run spilling tapes (F_SPILL, kernels.h KParams::spill):
+    // grow-only, sized per call before anything of the call is queued (spill_reserve); the
+    // launches of one call that may overlap take disjoint regions of it, and a later call's
+    // launches are ordered after them (the side streams fork from and join into `stream`)
+    uint32_t* d_spill = nullptr;
+    size_t spill_bytes = 0;
 };
 
 // One compile at a time, handed to a worker thread that waits on a condition variable (a thread
@@ -273,6 +279,9 @@ struct mh_tapeset {
     // mh_eval_values_tables only; the (table id, key words) pairs the tapes' nodes name
     bool has_tables = false;
     std::vector<std::pair<uint32_t, uint32_t>> lookups;
+    // spill slots per tape, the parts after the tapes (0: the tape does not spill; F_SPILL tapes
+    // run in mh::kSpillVariant with a region of the ctx's spill memory)
+    std::vector<uint32_t> spills;
 };
 
 // The device block the sets of one mh_tables_create_many share: freed with the last handle.
@@ -422,6 +431,59 @@ int32_t ctx_batch_bufs(mh_ctx* ctx, size_t bytes) {
         MH_HIP(hipMalloc(&ctx->d_batch, n));
         ctx->d_batch_bytes = n;
     }
+    return MH_OK;
+}
+
+// The regions the spilling launches of one call take out of the ctx's spill memory: take() per
+// launch while the call is planned, spill_reserve() once before anything is queued, at() when the
+// launch's KParams are made.
+struct SpillPlan {
+    uint64_t words = 0;
+    // the launch's region (its offset in words) for `waves` waves of `slots` slots each
+    uint64_t take(uint64_t waves, uint32_t slots) {
+        const uint64_t off = words;
+        words += mh::spill_words(waves, slots);
+        return off;
+    }
+};
+
+// the most spill slots a tape of ids [b, e) uses (a launch's KParams::spill_slots)
+uint32_t max_spills(const mh_tapeset* ts, const uint32_t* b, const uint32_t* e) {
+    uint32_t m = 0;
+    for (; b != e; ++b) m = std::max(m, ts->spills[*b]);
+    return m;
+}
+
+// Makes the ctx's spill memory hold `words` words.  Called before a call queues anything: a call
+// whose spill areas exceed the cap (256 MiB; MH_SPILL_CAP_MB for experiments) is refused whole.
+// The memory grows only here, after everything queued on the ctx's streams has finished, so no
+// launch can still be using the block that is freed.
+int32_t spill_reserve(mh_ctx* ctx, uint64_t words) {
+    if (words == 0) return MH_OK;
+    static const uint64_t cap = [] {
+        const char* e = std::getenv("MH_SPILL_CAP_MB");
+        const uint64_t mb = e ? std::strtoull(e, nullptr, 10) : 0;
+        return (mb ? mb : 256ull) << 20;
+    }();
+    const uint64_t bytes = words * sizeof(uint32_t);
+    if (bytes > cap)
+        return set_err(MH_E_UNSUPPORTED,
+                       "the launch's spill areas take " + std::to_string(bytes) +
+                           " bytes, more than the cap of " + std::to_string(cap) +
+                           " (tapes with more live values than registers; fewer rows per run fit)");
+    if (bytes <= ctx->spill_bytes) return MH_OK;
+    MH_HIP(hipStreamSynchronize(ctx->stream));
+    for (hipStream_t sd : ctx->side)
+        if (sd) MH_HIP(hipStreamSynchronize(sd));
+    if (ctx->d_spill) MH_HIP(hipFree(ctx->d_spill));
+    ctx->d_spill = nullptr;
+    ctx->spill_bytes = 0;
+    size_t n = (size_t)1 << 20;
+    while (n < bytes) n <<= 1;
+    hipError_t e = hipMalloc(&ctx->d_spill, n);
+    if (e != hipSuccess)
+        return set_err(MH_E_NOMEM, std::string("spill memory: ") + hipGetErrorString(e));
+    ctx->spill_bytes = n;
     return MH_OK;
 }
 
@@ -602,6 +664,7 @@ void ctx_free(mh_ctx* ctx) {
     }
     if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
     if (ctx->d_masks) (void)hipFree(ctx->d_masks);
+    if (ctx->d_spill) (void)hipFree(ctx->d_spill);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->d_buf) (void)hipFree(ctx->d_buf);
     if (ctx->h_buf) (void)hipHostFree(ctx->h_buf);
@@ -754,6 +817,7 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
     mh::ConstIndex dindex;
     std::vector<mh_dev_tape> heads(n_tapes);
     std::vector<mh_tape_info> info(n_tapes);
+    std::vector<uint32_t> spills(n_tapes, 0);  // slots per tape, then per part
     std::vector<uint32_t> ids, bucket_off(mh::kNumVariants + 1, 0);
     // conjunct-parallel parts (mh_tapeset): heads n_tapes.. and their buckets
     std::vector<uint32_t> ids_unsplit, part_ids, part_parent, split_tab;
@@ -783,7 +847,7 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
                 }
             }
             const int32_t r = mh::compile_tape(tn, nn, consts, n_consts, n_vars, dconsts, dindex,
-                                               w, ct, err);
+                                               w, ct, err, true);
             if (r == MH_OK && use_cache) {
                 if (ctx->compile_cache_words + w.size() > kCacheWords) {
                     ctx->compile_cache.clear();
@@ -803,6 +867,7 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
             if (r != MH_OK) return set_err(r, "tape " + std::to_string(t) + ": " + err);
             heads[t] = mh_dev_tape{0, ct.n_insns, ct.root_bool, ct.n_regs};
             info[t] = mh_tape_info{ct.n_nodes, ct.n_insns, ct.n_regs, ct.features, ct.alg_ops};
+            spills[t] = ct.n_spills;
         }
         // conjunct-parallel parts of the long tapes (a query round's latency is its longest
         // tape walked by one wave per SIMD: parts walk in parallel, mh_run_async); MH_SPLIT_INSNS
@@ -816,6 +881,7 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
         std::vector<std::vector<uint32_t>> pw;
         std::vector<mh_tape_info> pinfo;
         std::vector<mh_dev_tape> pheads;
+        std::vector<uint32_t> pspills;
         for (uint32_t t = 0; split_min && t < n_tapes; ++t) {
             if (info[t].n_insns < split_min || !heads[t].root_bool) continue;
             if (info[t].features & F_TABLE) continue;  // never run by mh_run_async
@@ -837,11 +903,13 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
                 pw.push_back(std::move(w));
                 pinfo.push_back(mh_tape_info{ct.n_nodes, ct.n_insns, ct.n_regs, ct.features, ct.alg_ops});
                 pheads.push_back(mh_dev_tape{0, ct.n_insns, ct.root_bool, ct.n_regs});
+                pspills.push_back(ct.n_spills);
             }
             if (!ok) {
                 pw.resize(p0);
                 pinfo.resize(p0);
                 pheads.resize(p0);
+                pspills.resize(p0);
                 continue;
             }
             split_tab.insert(split_tab.end(), {t, n_tapes + (uint32_t)p0, (uint32_t)parts.size()});
@@ -882,6 +950,7 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
             }
         }
         off_parts[mh::kNumVariants] = (uint32_t)part_ids.size();
+        spills.insert(spills.end(), pspills.begin(), pspills.end());
     } catch (const std::bad_alloc&) {
         return set_err(MH_E_NOMEM, "host allocation during compile");
     }
@@ -913,6 +982,7 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
         ts->bucket_off_parts[v] = off_parts[v];
     }
     ts->info = std::move(info);
+    ts->spills = std::move(spills);
     for (const mh_tape_info& ti : ts->info) ts->has_tables |= (ti.features & F_TABLE) != 0;
     for (uint32_t t = 0; t < n_tapes; ++t)
         mh::tape_lookups(nodes + tape_offsets[t], (size_t)(tape_offsets[t + 1] - tape_offsets[t]),
@@ -1002,6 +1072,13 @@ int32_t mh_tapes_destroy(mh_tapeset* ts) {
     mh_ctx* ctx = ts->ctx;
     delete ts;
     ctx_unref(ctx);
+    return MH_OK;
+}
+
+int32_t mh_tapes_spills(const mh_tapeset* ts, uint32_t* out, uint32_t n_tapes) {
+    if (!ts || !out) return set_err(MH_E_INVALID, "null argument");
+    if (n_tapes > ts->n_tapes) return set_err(MH_E_INVALID, "n_tapes exceeds the tape set");
+    std::copy(ts->spills.begin(), ts->spills.begin() + n_tapes, out);
     return MH_OK;
 }
 
@@ -1476,6 +1553,20 @@ int32_t mh_run_async(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first, uin
             if (phi[v] != plo[v] && !mh::variant_fits(v, p.capacity)) return refuse_capacity(p.capacity);
         }
     }
+    // the spilling tapes' launches (whole tapes, parts): a region each, which may overlap on the
+    // side streams; sized and refused before anything is queued
+    SpillPlan spill;
+    uint64_t spill_off[2] = {0, 0};
+    uint32_t spill_slots[2] = {0, 0};
+    for (int part = 0; part < 2; ++part) {
+        const uint32_t* b = part ? plo[mh::kSpillVariant] : lo[mh::kSpillVariant];
+        const uint32_t* e = part ? phi[mh::kSpillVariant] : hi[mh::kSpillVariant];
+        if (b == e || row_count == 0) continue;
+        spill_slots[part] = max_spills(ts, b, e);
+        spill_off[part] = spill.take(
+            mh::sieve_launch_waves(row_count, (uint32_t)(e - b), part != 0), spill_slots[part]);
+    }
+    if (int32_t r = spill_reserve(ctx, spill.words)) return r;
     const uint64_t mask_stride = mh::sieve_mask_stride(row_count);
     if (part_hi > part_lo) {
         const size_t need = (size_t)(part_hi - part_lo) * mask_stride * sizeof(unsigned long long);
@@ -1552,6 +1643,10 @@ int32_t mh_run_async(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first, uin
             q.tape_ids = d_ids + (launches[i].b - ids.data());
         }
         q.n_ids = (uint32_t)(launches[i].e - launches[i].b);
+        if (launches[i].variant == mh::kSpillVariant) {
+            q.spill = ctx->d_spill + spill_off[launches[i].part];
+            q.spill_slots = spill_slots[launches[i].part];
+        }
         // launch 0 on the ctx stream, the others round-robin over the side streams
         hipStream_t s = n_side && i ? ctx->side[(i - 1) % n_side] : ctx->stream;
         MH_HIP(mh::launch_sieve(q, launches[i].variant, s));
@@ -1792,6 +1887,18 @@ int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jo
                 return job_err(job, MH_E_UNSUPPORTED, g_err);
             }
         }
+    // the spilling tapes' launch (at most one: the spill variant is a register class of its own):
+    // every segment of it names the launch's region and its slot count, the most over the
+    // launch's tapes; a wave's area is picked by the launch's workgroup index
+    SpillPlan spill;
+    uint32_t spill_slots = 0;
+    for (const mh::batch::Segment& sg : plan.segments)
+        if (sg.last_bucket == mh::kSpillVariant) {
+            const uint32_t* lo = jp[sg.job].lo[sg.first_bucket];
+            spill_slots = std::max(spill_slots, max_spills(jobs[sg.job].ts, lo, lo + sg.n_ids));
+        }
+    for (const auto& l : plan.launches)
+        if (l.variant == mh::kSpillVariant) (void)spill.take(l.count, spill_slots);
     // the device block: segments' KParams | GenJob[] | ResultJob[] | block tables | guides
     const auto align = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_seg = 0;
@@ -1805,6 +1912,7 @@ int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jo
         up_bytes = align(up_bytes + jp[i].L.words * sizeof(uint32_t));
     }
     if (int32_t r = use_device(ctx)) return r;
+    if (int32_t r = spill_reserve(ctx, spill.words)) return r;
     if (int32_t r = ctx_batch_bufs(ctx, up_bytes)) return r;
     void* dres_v = nullptr;
     void* hres_v = nullptr;
@@ -1847,6 +1955,10 @@ int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jo
         p.hit_count = fh + j.tape_count;
         p.tape_ids = j.ts->d_ids + (jp[sg.job].lo[sg.first_bucket] - j.ts->ids.data());
         p.n_ids = sg.n_ids;
+        if (sg.last_bucket == mh::kSpillVariant) {
+            p.spill = ctx->d_spill;
+            p.spill_slots = spill_slots;
+        }
         h_seg[si] = p;
     }
     if (!plan.blocks.empty())
@@ -1911,6 +2023,10 @@ int32_t mh_eval_values(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape, const m
     if (int32_t r = use_device(ctx)) return r;
     const uint32_t variant = mh::variant_of(ts->info[tape].n_regs, ts->info[tape].features);
     if (!mh::variant_fits(variant, as->stride)) return refuse_capacity(as->stride);
+    SpillPlan spill;
+    if (variant == mh::kSpillVariant)
+        (void)spill.take(mh::sieve_launch_waves(row_count, 1, false), ts->spills[tape]);
+    if (int32_t r = spill_reserve(ctx, spill.words)) return r;
     // the production sieve kernel in values mode, over a one-tape list
     uint32_t* d = nullptr;
     MH_HIP(hipMalloc(&d, (8 * row_count + 8) * sizeof(uint32_t)));
@@ -1921,6 +2037,10 @@ int32_t mh_eval_values(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape, const m
     p.first_hit = reinterpret_cast<unsigned long long*>(d_id + 2);
     p.hit_count = reinterpret_cast<unsigned long long*>(d_id + 4);
     p.values_out = d;
+    if (variant == mh::kSpillVariant) {
+        p.spill = ctx->d_spill;
+        p.spill_slots = ts->spills[tape];
+    }
     // copies on the ctx stream: the first use of the null stream creates a hardware queue
     // (20.6 ms, profiles/r04x), which a query's first definitions evaluation paid
     const uint32_t ids[8] = {tape, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0, 0};
@@ -1998,6 +2118,16 @@ int32_t mh_eval_values_jobs(mh_ctx* ctx, const mh_values_job* jobs, uint32_t n_j
     if (slots * 8 >= (1ull << 31))
         return set_err(MH_E_INVALID, "mh_eval_values_jobs: values of 2^31 words or more in one call");
     const mh::values::Plan plan = mh::values::plan(shapes.data(), n_jobs);
+    // the spilling tapes' launch: one region, the launch's workgroup picks the wave's area
+    SpillPlan spill;
+    uint32_t spill_slots = 0;
+    for (const mh::values::Segment& sg : plan.segments)
+        if (sg.variant == mh::kSpillVariant)
+            spill_slots = std::max(spill_slots,
+                                   max_spills(jobs[sg.job].ts, plan.ids.data() + sg.first,
+                                              plan.ids.data() + sg.first + sg.n_ids));
+    for (const auto& l : plan.launches)
+        if (l.variant == mh::kSpillVariant) (void)spill.take(l.count, spill_slots);
     // the upload block: segments' KParams | block table | sorted ids
     const auto align = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_seg = 0;
@@ -2006,6 +2136,7 @@ int32_t mh_eval_values_jobs(mh_ctx* ctx, const mh_values_job* jobs, uint32_t n_j
     const size_t up_bytes = align(o_ids + plan.ids.size() * sizeof(uint32_t));
     const size_t val_bytes = (size_t)slots * 8 * sizeof(uint32_t);
     if (int32_t r = use_device(ctx)) return r;
+    if (int32_t r = spill_reserve(ctx, spill.words)) return r;
     if (int32_t r = ctx_batch_bufs(ctx, up_bytes)) return r;
     void* dval_v = nullptr;
     void* hval_v = nullptr;
@@ -2027,6 +2158,10 @@ int32_t mh_eval_values_jobs(mh_ctx* ctx, const mh_values_job* jobs, uint32_t n_j
         p.tape_ids = d_ids + sg.first;
         p.n_ids = sg.n_ids;
         p.values_out = dval + 8 * (size_t)sg.first;
+        if (sg.variant == mh::kSpillVariant) {
+            p.spill = ctx->d_spill;
+            p.spill_slots = spill_slots;
+        }
         h_seg[si] = p;
     }
     std::memcpy(hb + o_blk, plan.blocks.data(), plan.blocks.size() * sizeof(mh::batch::BlockEntry));
@@ -2096,6 +2231,16 @@ static int32_t eval_values_rows(mh_ctx* ctx, const mh_tapeset* ts, const mh_tabl
         if (tapes[a.second] != tapes[b.second]) return tapes[a.second] < tapes[b.second];
         return a.second < b.second;
     });
+    // the spilling tapes' launch (the launches queue on one stream: one region)
+    SpillPlan spill;
+    uint32_t spill_slots = 0, n_spill = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        if (by_var[i].first == mh::kSpillVariant) {
+            ++n_spill;
+            spill_slots = std::max(spill_slots, ts->spills[tapes[by_var[i].second]]);
+        }
+    if (n_spill) (void)spill.take(mh::sieve_launch_waves(row_count, n_spill, false), spill_slots);
+    if (int32_t r = spill_reserve(ctx, spill.words)) return r;
     // device block: values [n][8][rows], ids [n], first_hit / hit_count [top + 1] each (scratch:
     // the kernel's count-mode bookkeeping, indexed by tape id)
     const size_t nv = (size_t)8 * n * row_count;  // value words
@@ -2126,6 +2271,10 @@ static int32_t eval_values_rows(mh_ctx* ctx, const mh_tapeset* ts, const mh_tabl
         p.first_hit = reinterpret_cast<unsigned long long*>(d_res);
         p.hit_count = reinterpret_cast<unsigned long long*>(d_res + 2 * ((size_t)top + 1));
         p.values_out = d + 8 * (size_t)i * row_count;
+        if (by_var[i].first == mh::kSpillVariant) {
+            p.spill = ctx->d_spill;
+            p.spill_slots = spill_slots;
+        }
         e = mh::launch_sieve(p, by_var[i].first, ctx->stream);
         ++launches;
         i = j;
@@ -2565,6 +2714,12 @@ int32_t mh_repair_score(mh_repair* r, const mh_tapeset* ts, uint32_t tape_first,
         hi[v] = std::lower_bound(lo[v], e, tape_first + tape_count);
         if (hi[v] != lo[v] && !mh::variant_fits(v, p.capacity)) return refuse_capacity(p.capacity);
     }
+    SpillPlan spill;
+    const uint32_t *slo = lo[mh::kSpillVariant], *shi = hi[mh::kSpillVariant];
+    const uint32_t spill_slots = max_spills(ts, slo, shi);
+    if (shi != slo)
+        (void)spill.take(mh::sieve_launch_waves(row_count, (uint32_t)(shi - slo), true), spill_slots);
+    if (int32_t rc = spill_reserve(ctx, spill.words)) return rc;
     r->scored = r->selected = false;
     if (int32_t rc = repair_span(ctx, false)) return rc;
     for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
@@ -2572,6 +2727,10 @@ int32_t mh_repair_score(mh_repair* r, const mh_tapeset* ts, uint32_t tape_first,
         mh::KParams q = p;
         q.tape_ids = ts->d_ids + (lo[v] - ts->ids.data());
         q.n_ids = (uint32_t)(hi[v] - lo[v]);
+        if (v == mh::kSpillVariant) {
+            q.spill = ctx->d_spill;
+            q.spill_slots = spill_slots;
+        }
         MH_HIP(mh::launch_sieve(q, v, ctx->stream));
     }
     MH_HIP(mh::launch_fail_count(r->d_masks, stride, tape_count, (uint32_t)row_count, r->d_fail,

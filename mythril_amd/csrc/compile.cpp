@@ -1356,7 +1356,7 @@ int32_t compile_tape_once(const mh_node* nodes, size_t n_nodes, const uint32_t* 
                           uint32_t n_consts, uint32_t n_vars, std::vector<uint32_t>& dconsts,
                           ConstIndex& dconst_index,
                           std::vector<uint32_t>& words, CompiledTape& out, std::string& err,
-                          bool hold_vars, bool sc);
+                          bool hold_vars, bool sc, bool allow_spill = false);
 
 }  // namespace
 
@@ -1372,7 +1372,8 @@ int32_t compile_tape_once(const mh_node* nodes, size_t n_nodes, const uint32_t* 
 int32_t compile_tape(const mh_node* nodes, size_t n_nodes, const uint32_t* consts,
                      uint32_t n_consts, uint32_t n_vars, std::vector<uint32_t>& dconsts,
                      ConstIndex& dconst_index,
-                     std::vector<uint32_t>& words, CompiledTape& out, std::string& err) {
+                     std::vector<uint32_t>& words, CompiledTape& out, std::string& err,
+                     bool allow_spill) {
     static thread_local int hint = 0;  // index into the attempt list of the last success
     const bool hold = n_vars > MH_MAX_PRELOAD && !std::getenv("MH_NO_HOLD_VARS");
     static const uint32_t kSizes[4] = {0u, 8u, 32u, 256u};
@@ -1405,6 +1406,21 @@ int32_t compile_tape(const mh_node* nodes, size_t n_nodes, const uint32_t* const
             return r;
         }
     }
+    if (!allow_spill) return r;
+    // every attempt ran out of registers: the tape as lowered (no rematerialisation, no held
+    // columns, the short-circuit order) with values spilled to the wave's spill area where the
+    // register file is full (D_SPILL / D_FILL, dev_isa.h).  Never tried before the others -- a
+    // tape that fits keeps the code it had -- so it is not the hint either.
+    err.clear();
+    words.resize(words0);
+    if (dconsts.size() != dconsts0) {
+        dconsts.resize(dconsts0);
+        for (auto i = dconst_index.begin(); i != dconst_index.end();)
+            i = i->second >= dconsts0 / 8 ? dconst_index.erase(i) : std::next(i);
+    }
+    r = compile_tape_once(nodes, n_nodes, consts, n_consts, n_vars, dconsts, dconst_index, words,
+                          out, err, false, true, true);
+    out.n_nodes = (uint32_t)n_nodes;
     return r;
 }
 
@@ -1493,7 +1509,8 @@ int32_t compile_tape_once(const mh_node* nodes, size_t n_nodes, const uint32_t* 
                           uint32_t n_consts, uint32_t n_vars, std::vector<uint32_t>& dconsts,
                           ConstIndex& dconst_index,
                           std::vector<uint32_t>& words, CompiledTape& out, std::string& err,
-                          bool hold_vars, bool sc) {
+                          bool hold_vars, bool sc, bool allow_spill) {
+    out.n_spills = 0;
     SsaTape st;
     if (int32_t r = lower_tape_ssa(nodes, n_nodes, consts, n_consts, n_vars, dconsts,
                                    dconst_index, st, err, 0, false, hold_vars))
@@ -1570,6 +1587,134 @@ int32_t compile_tape_once(const mh_node* nodes, size_t n_nodes, const uint32_t* 
     for (int r = MH_NR_MAX - 1; r >= n_pinned; --r) free_regs.push_back(r);
     std::vector<char> wb(code.size(), 0);
     int peak = n_pinned;  // highest register index used + 1
+    // allow_spill: a value's register changes along the tape, so the registers each instruction
+    // names are recorded per instruction (ra: -1 = the first operand comes out of X after a fill),
+    // with the spill code that runs before it (pre: pairs of slot words)
+    std::vector<int> ra, rb, rc, rd;
+    std::vector<std::vector<uint32_t>> pre;
+    uint32_t n_slots = 0;
+    if (allow_spill) {
+        const size_t n = code.size();
+        ra.assign(n, 0), rb.assign(n, 0), rc.assign(n, 0), rd.assign(n, 0);
+        pre.resize(n);
+        // every register use of a value, ascending: the eviction victim is the live value whose
+        // next use lies furthest ahead
+        std::vector<std::vector<int>> uses(nv);
+        for (int i = 0; i < (int)n; ++i) {
+            const VInsn& v = code[i];
+            for (int r : {lda[i] ? v.a : -1, v.cidx >= 0 ? -1 : v.b, v.c})
+                if (r >= n_pinned && (uses[r].empty() || uses[r].back() != i)) uses[r].push_back(i);
+        }
+        std::vector<size_t> upos(nv, 0);
+        std::vector<int> owner(MH_NR_MAX, -1), slot_of(nv, -1);
+        std::vector<uint32_t> free_slots;  // slots whose value is dead: the lowest is reused first
+        const uint32_t X = MH_NR_MAX;      // a tape that spills runs in the NR = 15 kernel
+        auto next_use = [&](int r, int i) {  // the first use of r after instruction i
+            size_t& k = upos[r];
+            while (k < uses[r].size() && uses[r][k] <= i) ++k;
+            return k < uses[r].size() ? uses[r][k] : INT32_MAX;
+        };
+        // a register for instruction i: a free one, else the one of the victim, spilled before i
+        // unless its slot already holds it (values are SSA: one D_SPILL per value)
+        auto get_reg = [&](int i, const int* keep) {
+            if (!free_regs.empty()) {
+                auto it = std::min_element(free_regs.begin(), free_regs.end());
+                const int p = *it;
+                free_regs.erase(it);
+                return p;
+            }
+            int best = -1, best_use = -1;
+            for (int p = n_pinned; p < MH_NR_MAX; ++p) {
+                const int r = owner[p];
+                if (r < 0 || r == keep[0] || r == keep[1] || r == keep[2]) continue;
+                const int u = next_use(r, i);
+                if (u > best_use) best = p, best_use = u;
+            }
+            if (best < 0) return -1;
+            const int r = owner[best];
+            if (slot_of[r] < 0) {
+                if (free_slots.empty()) {
+                    slot_of[r] = (int)n_slots++;
+                } else {
+                    auto it = std::min_element(free_slots.begin(), free_slots.end());
+                    slot_of[r] = (int)*it;
+                    free_slots.erase(it);
+                }
+                pre[i].push_back((uint32_t)best);
+                pre[i].push_back(D_SPILL | (256u << 8) | ((uint32_t)slot_of[r] << 17));
+            }
+            phys[r] = -1;
+            owner[best] = -1;
+            return best;
+        };
+        for (int i = 0; i < (int)n; ++i) {
+            const VInsn& v = code[i];
+            const int ops[3] = {lda[i] ? v.a : -1, v.cidx >= 0 ? -1 : v.b, v.c};
+            int* regs[3] = {&ra[i], &rb[i], &rc[i]};
+            for (int k = 0; k < 3; ++k) {
+                const int r = ops[k];
+                if (r < 0) continue;
+                if (phys[r] < 0) {  // evicted: back from its slot before this instruction
+                    if (slot_of[r] < 0) {
+                        err = "internal: operand neither in a register nor spilled";
+                        return MH_E_INVALID;
+                    }
+                    uint32_t to;
+                    if (k == 0 && r != ops[1] && r != ops[2]) {
+                        to = X;  // X is dead where an instruction loads its first operand
+                    } else {
+                        const int p = get_reg(i, ops);
+                        if (p < 0) {
+                            err = "register pressure: no register to fill an operand into";
+                            return MH_E_UNSUPPORTED;
+                        }
+                        to = (uint32_t)p;
+                        phys[r] = p;
+                        owner[p] = r;
+                    }
+                    pre[i].push_back(X | (to << 16));
+                    pre[i].push_back(D_FILL | (256u << 8) | ((uint32_t)slot_of[r] << 17));
+                    if (to == X) {
+                        *regs[k] = -1;
+                        continue;
+                    }
+                }
+                *regs[k] = phys[r];
+            }
+            for (int k = 0; k < 3; ++k) {
+                const int r = ops[k];
+                if (r < n_pinned) continue;
+                bool dup = false;
+                for (int j = 0; j < k; ++j) dup |= ops[j] == r;
+                if (dup || last_use[r] != i) continue;
+                if (phys[r] >= 0) {
+                    free_regs.push_back(phys[r]);
+                    owner[phys[r]] = -1;
+                    phys[r] = -1;
+                }
+                if (slot_of[r] >= 0) free_slots.push_back((uint32_t)slot_of[r]);
+            }
+            if (!needs_reg[v.d]) continue;
+            const int p = get_reg(i, ops);
+            if (p < 0) {
+                err = "register pressure: no register for a result";
+                return MH_E_UNSUPPORTED;
+            }
+            phys[v.d] = p;
+            owner[p] = v.d;
+            rd[i] = p;
+            wb[i] = 1;
+        }
+        if (n_slots > MH_SPILL_SLOTS_MAX) {
+            err = "register pressure exceeds " + std::to_string(MH_NR_MAX) + " registers and " +
+                  std::to_string(MH_SPILL_SLOTS_MAX) + " spill slots (" + std::to_string(n_slots) +
+                  " needed)";
+            return MH_E_UNSUPPORTED;
+        }
+        peak = MH_NR_MAX;
+        if (n_slots) out.features |= F_SPILL | F_CPLX;
+        out.n_spills = n_slots;
+    } else
     for (int i = 0; i < (int)code.size(); ++i) {
         const VInsn& v = code[i];
         const int ops[3] = {lda[i] ? v.a : -1, v.cidx >= 0 ? -1 : v.b, v.c};
@@ -1609,10 +1754,23 @@ int32_t compile_tape_once(const mh_node* nodes, size_t n_nodes, const uint32_t* 
     for (size_t i = 0; i < code.size(); ++i) {
         const VInsn& v = code[i];
         auto P = [&](int r) -> uint32_t { return (r < 0 || phys[r] < 0) ? 0u : (uint32_t)phys[r]; };
-        const uint32_t a = lda[i] ? P(v.a) : nrx;
-        const uint32_t d = wb[i] ? P(v.d) : nrx;
-        const uint32_t b = v.cidx >= 0 ? 0u : P(v.b);
-        const uint32_t c = P(v.c);
+        uint32_t a = lda[i] ? P(v.a) : nrx;
+        uint32_t d = wb[i] ? P(v.d) : nrx;
+        uint32_t b = v.cidx >= 0 ? 0u : P(v.b);
+        uint32_t c = P(v.c);
+        if (allow_spill) {  // the registers as they were at this instruction, after its spill code
+            a = lda[i] && ra[i] >= 0 ? (uint32_t)ra[i] : nrx;
+            d = wb[i] ? (uint32_t)rd[i] : nrx;
+            b = v.cidx >= 0 ? 0u : (uint32_t)rb[i];
+            c = (uint32_t)rc[i];
+            for (size_t k = 0; k < pre[i].size(); k += 2) {
+                if (pos() % MH_WINDOW + 1 > MH_WINDOW - 1) {
+                    put(0, D_WINDOW);
+                    while (pos() % MH_WINDOW) put(0, 0);
+                }
+                put(pre[i][k], pre[i][k + 1]);
+            }
+        }
         uint32_t op = v.op;
         uint32_t w1;
         if (v.op == D_KECCAK || v.op == D_LOOKUP) {

@@ -18,6 +18,7 @@ struct CompiledTape {
     uint32_t root_bool = 0;
     uint32_t features = 0;
     uint64_t alg_ops = 0;
+    uint32_t n_spills = 0;  // spill slots the tape uses (features & F_SPILL iff > 0)
 };
 
 // One instruction of a lowered tape in SSA form (before the interpreter's accumulator pass and
@@ -87,10 +88,14 @@ void sample_bools(const SsaTape& st, const std::vector<uint32_t>& pool, uint32_t
 
 // Lower one tape.  Appends its instruction words (2 per instruction) to `words` and any new
 // constants to the shared device pool `dconsts` (8 limbs each, deduplicated via dconst_index).
+// allow_spill: a tape that runs out of registers in every attempt is compiled once more with
+// spill code (D_SPILL / D_FILL, out.n_spills slots) instead of being refused; only a caller
+// whose machine has the spill hooks of exec.h's step() asks for it.
 int32_t compile_tape(const mh_node* nodes, size_t n_nodes, const uint32_t* consts,
                      uint32_t n_consts, uint32_t n_vars, std::vector<uint32_t>& dconsts,
                      ConstIndex& dconst_index,
-                     std::vector<uint32_t>& words, CompiledTape& out, std::string& err);
+                     std::vector<uint32_t>& words, CompiledTape& out, std::string& err,
+                     bool allow_spill = false);
 
 // mh_tables_create's host half: validates the caller's tables (include/mythril_hip.h: nws in
 // 1..3, keys strictly ascending, every table inside its arrays) and packs them into the device

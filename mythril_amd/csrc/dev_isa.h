@@ -24,6 +24,17 @@
 //             R[b], R[c], little-endian slices of the key (LOW word first, unlike KECCAK's
 //             left-aligned message words); X = the value table `table` holds at that key, else
 //             the table's else value (hit = 1: the Bool "the key is in the table")
+//   D_SPILL / D_FILL (F_SPILL tapes only: the allocator ran out of registers, compile.cpp): the
+//             wave owns a spill area of the launch's spill_slots slots of 256 bits per lane in
+//             device memory (kernels.h KParams::spill); D_SPILL copies R[a'] to slot aux, D_FILL
+//             copies slot aux to R[d'].  Unlike every other instruction neither computes into X:
+//             D_SPILL leaves X and the registers alone, D_FILL changes only its target (which is
+//             X itself when d' = NRX).  The allocator needs X kept, because the instruction a
+//             fill serves may take its first operand from X; on the device a fill into a register
+//             costs the driver one more commit for it (X fetched, the target committed, X
+//             committed back), a fill into X costs one.  D_FILL's a' field is NRX (the fetch of
+//             X), b and c are 0.  A value is spilled at most once (values are SSA) and every
+//             D_FILL names a slot an earlier D_SPILL of the same tape wrote.
 // Ops below D_FIRST_COMPLEX run in the hand-written assembly core (asm_core.inc, threaded
 // code: one computed jump per instruction); the others in C++ (exec.h).  Narrow signed
 // compares, sign extension and arithmetic shifts are lowered by the host onto asm ops
@@ -103,6 +114,8 @@ enum mh_dop : uint8_t {
                                    // R[c] == 0 gives the low 256 bits of X op y (else 0)
     D_LOOKUP,                      // X = table aux at the key X, R[b], R[c] (below); after D_MULMOD,
                                    // so D_LOADVAR and the asm core's slots keep their numbers
+    D_SPILL,                       // spill slot aux of this wave = R[a']; X and R stay as they were
+    D_FILL,                        // R[d'] = spill slot aux (d' = NRX: X); nothing else changes
     D_NUM_OPS
 };
 
@@ -159,7 +172,13 @@ enum { F_YC = 1u << 31 };
 // F_KECCAK or F_EVM runs entirely in the asm core (a kernel without the C++ path: fewer VGPRs,
 // more waves).  F_DIV is informational (division runs in the asm core).
 enum { F_DIV = 1, F_KECCAK = 2, F_EVM = 4, F_CPLX = 8 /* other C++ ops */,
-       F_TABLE = 16 /* D_LOOKUP: the tape reads a table set (mh_tables) */ };
+       F_TABLE = 16 /* D_LOOKUP: the tape reads a table set (mh_tables) */,
+       F_SPILL = 32 /* D_SPILL / D_FILL: the tape needs a spill area (a kernel of its own) */ };
+// spill slots one tape may use (aux names the slot); beyond it the compile is refused
+#define MH_SPILL_SLOTS_MAX 256
+static_assert(MH_SPILL_SLOTS_MAX <= MH_AUX_MAX + 1, "a spill slot is named by aux");
+// words of one wave's spill slot: 8 limbs x 64 lanes
+#define MH_SPILL_SLOT_WORDS 512
 
 // Device layout of a table set (one u32 buffer; the host validates it, mh_tables_create, and
 // the kernel trusts it).  Word 0: the number of tables.  Then one header of MH_TABLE_HEAD words

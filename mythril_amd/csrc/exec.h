@@ -13,6 +13,9 @@
 //   void lookup(u32 table, u32 nw, const u32* k0, const u32* k1, const u32* k2, u32 hit, u32* z);
 //                                     D_LOOKUP (FEAT & F_TABLE only): table_lookup() below over
 //                                     the machine's table set
+//   void spill(u32 slot, const u32* v);  D_SPILL / D_FILL (FEAT & F_SPILL only): this row's slot
+//   void fill(u32 slot, u32* v);         of the spill area (per wave on the device, per row on
+//                                        the host)
 // FEAT (dev_isa.h F_DIV | F_KECCAK | F_EVM) compiles the heavy handlers in or out, so a tape
 // set without them runs a kernel with a smaller register budget (higher occupancy).
 #pragma once
@@ -188,6 +191,20 @@ MH_FN u32 step(M& m, u32 w0, u32 w1, u32 ip) {
     const u32 a = w0 & 0xFFu, b = (w0 >> 8) & 0xFFu, d = (w0 >> 16) & 0xFFu, c = w0 >> 24;
     const u32 op = mh_base_op(w1 & 0xFFu), aux = (w1 >> 17) & MH_AUX_MAX;
     u32 x[8], y[8], z[8];
+    if constexpr ((FEAT & F_SPILL) != 0) {
+        // neither op computes into X (dev_isa.h): a spill changes nothing in the register file,
+        // a fill only its target
+        if (op == D_SPILL) {
+            m.read(a, x);
+            m.spill(aux, x);
+            return 1;
+        }
+        if (op == D_FILL) {
+            m.fill(aux, z);
+            m.write(d, z);
+            return 1;
+        }
+    }
     m.read(a, x);
     u32 len = 1;
     bool full_y;

@@ -33,7 +33,20 @@ struct KParams {
     uint32_t pad2;
     uint64_t mask_stride;           // waves of the run's grid (sieve_mask_stride)
     const uint32_t* tables;         // the table set D_LOOKUP reads (dev_isa.h layout), or null
+    // the spill variant only (F_SPILL tapes; null / 0 otherwise): this launch's region of the
+    // ctx's spill memory, and the slots every wave owns in it (the maximum over the launch's
+    // tapes).  Wave W of the launch -- linear workgroup index of the LAUNCH (not of a batch
+    // segment) x waves per workgroup + wave in the workgroup -- keeps slot s, limb k of lane l at
+    // word ((W * spill_slots + s) * 8 + k) * 64 + l: 256 contiguous bytes per limb, like a column
+    // load.  Lanes of rows outside the run spill there too (nothing is indexed by row).
+    uint32_t* spill;
+    uint32_t spill_slots;
+    uint32_t pad3;
 };
+// words of spill memory a launch of `waves` waves needs
+inline uint64_t spill_words(uint64_t waves, uint32_t spill_slots) {
+    return waves * spill_slots * MH_SPILL_SLOT_WORDS;
+}
 
 // Kernel variants: register-file size class (NR 7 / 9 / 15) x feature set (asm only / + C++
 // complex ops / + keccak / + keccak and the EVM helpers).  Keccak tapes get a kernel without the
@@ -44,13 +57,18 @@ inline uint32_t nr_class(uint32_t n_regs) {
 // Tapes with a table lookup (F_TABLE: the certifier's, never a query round's) get a feature class
 // of their own with every handler, one kernel per register class, numbered after the twelve.
 constexpr uint32_t kFirstTableVariant = 12;
+// Tapes that spill (F_SPILL: more live values than MH_NR_MAX registers, compile.cpp) run in one
+// kernel of their own, NR = 15 with every handler, the table lookup included, and the spill ops:
+// no other variant carries a case, a branch or a register for them.
+constexpr uint32_t kSpillVariant = 15;
 inline uint32_t variant_of(uint32_t n_regs, uint32_t features) {
+    if (features & F_SPILL) return kSpillVariant;
     if (features & F_TABLE) return kFirstTableVariant + nr_class(n_regs);  // 12..14
     const uint32_t fc = (features & F_EVM) ? 3u : (features & F_KECCAK) ? 2u
                         : (features & F_CPLX) ? 1u : 0u;
     return nr_class(n_regs) * 4 + fc;  // 0..11
 }
-constexpr uint32_t kNumVariants = 15;
+constexpr uint32_t kNumVariants = 16;
 // The complex-op variants (feature class != 0) load columns inside the asm core (run_lv) with a
 // 32-bit byte stride per limb plane: their buffers hold fewer than 2^30 rows per column.  The
 // asm-only variants index columns with 64-bit arithmetic and take any capacity.
@@ -60,6 +78,9 @@ inline bool variant_fits(uint32_t variant, uint64_t capacity) {
 }
 
 hipError_t launch_sieve(const KParams& p, uint32_t variant, hipStream_t stream);
+// waves launch_sieve starts for a run of row_count rows over n_ids tapes (what the spill variant's
+// region is sized by: spill_words(sieve_launch_waves(..), spill_slots))
+uint64_t sieve_launch_waves(uint64_t row_count, uint32_t n_ids, bool masks);
 hipError_t launch_generate(uint32_t* assign, uint64_t stride, uint64_t rows, uint32_t n_vars,
                            uint64_t seed, uint64_t base, hipStream_t stream);
 // Device form of mh_guide (pointers into one device buffer owned by the mh_assign).
@@ -100,7 +121,8 @@ hipError_t launch_enumerate(uint32_t* assign, uint64_t stride, uint64_t first, u
 // A batched round (mh_query_round_many; the tables are batch_plan.h's, on the device, read only).
 // Interpreter: workgroup i of the launch runs blocks[i] = {segment, row block, tape slice, slices}
 // with segs[segment]; `variant` serves every segment of the launch.  A round's launches are
-// table-free (`variant` < kFirstTableVariant); mh_eval_values_jobs (values_plan.h: one-row
+// table-free (`variant` < kFirstTableVariant, or kSpillVariant with segments that carry their
+// part of the launch's spill region); mh_eval_values_jobs (values_plan.h: one-row
 // segments in values mode, row block 0) also launches the table variants, whose segments each
 // carry their own `tables`.
 hipError_t launch_sieve_batch(const KParams* segs, const batch::BlockEntry* blocks,

@@ -17,7 +17,9 @@
 //
 // Kernel variants (kernels.h variant_of): NR in {7, 9, 15} x {asm only, + C++ overflow
 // predicates / unpinned columns, + keccak, + keccak/EVM}, and per NR one with every handler and
-// the table lookup (D_LOOKUP; mh_eval_values_tables and mh_eval_values_jobs only);
+// the table lookup (D_LOOKUP; mh_eval_values_tables and mh_eval_values_jobs only), and one more
+// NR = 15 kernel with all of that and D_SPILL / D_FILL for the tapes whose live values exceed the
+// register file (F_SPILL; the wave's spill area is device memory, KParams::spill);
 // mh_run launches one variant per non-empty bucket of tapes, so a tape set's simple tapes run
 // with the register budget (and occupancy) they need rather than the worst tape's.
 #include <hip/hip_runtime.h>
@@ -119,6 +121,19 @@ struct DevMachine {
                                            const u32* k2, u32 hit, u32* z) const {
         table_lookup(p->tables, table, nw, k0, k1, k2, hit, z);
     }
+    // D_SPILL / D_FILL (the F_SPILL variant only, which sets spill_lane): slot `slot` of this
+    // wave's spill area (kernels.h KParams::spill), one coalesced 256-byte row per limb
+    u32* spill_lane;  // the wave's area + this lane
+    __device__ __forceinline__ void spill(u32 slot, const u32* v) const {
+        u32* q = spill_lane + (u64)slot * MH_SPILL_SLOT_WORDS;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) q[k * 64] = v[k];
+    }
+    __device__ __forceinline__ void fill(u32 slot, u32* v) const {
+        const u32* q = spill_lane + (u64)slot * MH_SPILL_SLOT_WORDS;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = q[k * 64];
+    }
 };
 
 __device__ __forceinline__ u64 splitmix64(u64 x) {
@@ -144,7 +159,15 @@ __device__ __forceinline__ void exec_tape(DevMachine<NR>& m, const uint2* src, I
         const u32 at = MH_ASM_CORE_WINDOW ? win + ip : ip;
         const uint2* base = MH_ASM_CORE_WINDOW ? gsrc : gsrc + win;
         u32 back;
-        if constexpr (FEAT != 0 && MH_ASM_LOADVAR) {
+        // The spill variant takes the core without the in-core LOADVAR: a D_LOADVAR leaves it and
+        // the driver below loads the column (m.var).  run_lv's LOADVAR trusts its prefetch
+        // register (the column in flight, reset on entry) between two LOADVARs of one stay in
+        // the core, but the division body uses the same SGPR as the high half of a lane-mask
+        // temporary; after a re-entry the prefetch registers hold nothing, and a LOADVAR whose
+        // column equals what a division left there takes them for its column.  A spilled tape
+        // re-enters the core at every spill op, and its wide sets counted wrong that way on the
+        // MI355X; an exit per LOADVAR is the price on this path.
+        if constexpr (FEAT != 0 && MH_ASM_LOADVAR && (FEAT & F_SPILL) == 0) {
             // columns beyond the preloaded ones load inside the core (no exit per LOADVAR);
             // launch_sieve keeps capacity * 4 within 32 bits
             const u64 a = (u64)(uintptr_t)m.p->assign;
@@ -202,6 +225,35 @@ __device__ __forceinline__ void exec_tape(DevMachine<NR>& m, const uint2* src, I
             // back by asm -- the C++ code never touches the planes, so they stay in their VGPRs
             typedef typename AsmCore<NR>::v8_t v8_t;
             u32 z[8];
+            if constexpr ((FEAT & F_SPILL) != 0) {
+                // neither op computes into X (dev_isa.h).  D_SPILL: R[a'] out, nothing committed.
+                // D_FILL: a' names X, so the fetch takes X out; the commit writes the slot's value
+                // to X and R[d'], and, unless the target is X itself, a second one puts X back
+                if (op == D_SPILL || op == D_FILL) {
+                    const u32 slot = (w1 >> 17) & MH_AUX_MAX;
+                    v8_t xv, yv, cv;
+                    AsmCore<NR>::fetch(m.R.p0, m.R.p1, m.R.p2, m.R.p3, m.R.p4, m.R.p5, m.R.p6,
+                                       m.R.p7, ic.w0, ic.w1, ip, w0, w1, xv, yv, cv);
+                    if (op == D_SPILL) {
+                        u32 x[8];
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) x[k] = xv[k];
+                        m.spill(slot, x);
+                    } else {
+                        m.fill(slot, z);
+                        v8_t zv;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) zv[k] = z[k];
+                        AsmCore<NR>::commit(m.R.p0, m.R.p1, m.R.p2, m.R.p3, m.R.p4, m.R.p5,
+                                            m.R.p6, m.R.p7, w0, zv);
+                        if (((w0 >> 16) & 0xFFu) != (u32)NR)
+                            AsmCore<NR>::commit(m.R.p0, m.R.p1, m.R.p2, m.R.p3, m.R.p4, m.R.p5,
+                                                m.R.p6, m.R.p7, (u32)NR << 16, xv);
+                    }
+                    ip += 1u;
+                    continue;
+                }
+            }
             if (op == D_LOADVAR) {
                 // a column beyond the preloaded ones (wide query schemas): no operands to fetch
                 m.var((w1 >> 17) & MH_AUX_MAX, z);
@@ -266,12 +318,16 @@ struct GridCoords {
     __device__ __forceinline__ u32 bx() const { return blockIdx.x; }
     __device__ __forceinline__ u32 by() const { return blockIdx.y; }
     __device__ __forceinline__ u32 ny() const { return gridDim.y; }
+    // linear workgroup index of the launch (the spill variant's region arithmetic)
+    __device__ __forceinline__ u32 wg() const { return blockIdx.y * gridDim.x + blockIdx.x; }
 };
 struct TableCoords {
     u32 x, y, n;
     __device__ __forceinline__ u32 bx() const { return x; }
     __device__ __forceinline__ u32 by() const { return y; }
     __device__ __forceinline__ u32 ny() const { return n; }
+    // the launch's workgroup, not the segment's: a batch's segments share one spill region
+    __device__ __forceinline__ u32 wg() const { return blockIdx.x; }
 };
 
 template <int NR, int FEAT, int BLOCK, class Coords>
@@ -287,6 +343,10 @@ __device__ __forceinline__ void sieve_body(const KParams& p, const Coords at) {
     DevMachine<NR> m;
     m.p = &p;
     m.lrow = valid ? row : p.row_first;
+    if constexpr ((FEAT & F_SPILL) != 0) {
+        const u64 wave = (u64)at.wg() * (BLOCK / 64) + (tid >> 6);
+        m.spill_lane = p.spill + wave * p.spill_slots * MH_SPILL_SLOT_WORDS + (tid & 63u);
+    }
     preload<NR>(m, p);
     const u64 block_first = p.index_base + p.row_first + (u64)at.bx() * BLOCK;
     const u64 wave_first = block_first + (tid & ~63u);
@@ -732,15 +792,21 @@ __global__ void __launch_bounds__(256)
     if (cnt && hit_count) atomicAdd(&hit_count[t - result_base], cnt);
 }
 
+// grid y of a launch of `blocks` row blocks over n_ids tapes
+inline u64 launch_grid_y(u64 blocks, u32 n_ids, bool masks) {
+    // fewer row blocks than CUs: split the tapes over grid y until the chip has ~256 workgroups
+    u64 gy = 1;
+    if (blocks < 256) gy = std::min<u64>(n_ids, (256 + blocks - 1) / blocks);
+    // the parts of split tapes (conjunct-parallel short runs) each get their own workgroups up
+    // to 4096 in all: a part walked after another on the same workgroup gains no latency
+    if (masks && blocks < 4096) gy = std::max<u64>(gy, std::min<u64>(n_ids, 4096 / blocks));
+    return gy;
+}
+
 template <int NR, int FEAT, int BLOCK>
 hipError_t launch_block(const KParams& p, hipStream_t stream) {
     const u64 blocks = (p.row_count + BLOCK - 1) / BLOCK;
-    // fewer row blocks than CUs: split the tapes over grid y until the chip has ~256 workgroups
-    u64 gy = 1;
-    if (blocks < 256) gy = std::min<u64>(p.n_ids, (256 + blocks - 1) / blocks);
-    // the parts of split tapes (conjunct-parallel short runs) each get their own workgroups up
-    // to 4096 in all: a part walked after another on the same workgroup gains no latency
-    if (p.masks && blocks < 4096) gy = std::max<u64>(gy, std::min<u64>(p.n_ids, 4096 / blocks));
+    const u64 gy = launch_grid_y(blocks, p.n_ids, p.masks != nullptr);
     hipLaunchKernelGGL((sieve_kernel<NR, FEAT, BLOCK>), dim3((unsigned)blocks, (unsigned)gy),
                        dim3(BLOCK), 0, stream, p);
     return hipGetLastError();
@@ -755,6 +821,13 @@ hipError_t launch_variant(const KParams& p, hipStream_t stream) {
 }  // namespace
 
 namespace mh {
+
+uint64_t sieve_launch_waves(uint64_t row_count, uint32_t n_ids, bool masks) {
+    if (row_count == 0 || n_ids == 0) return 0;
+    const u64 b = (u64)sieve_block(row_count);
+    const u64 blocks = (row_count + b - 1) / b;
+    return blocks * launch_grid_y(blocks, n_ids, masks) * (b / 64);
+}
 
 uint64_t sieve_mask_stride(uint64_t row_count) {  // the waves of the run's workgroups
     const u64 b = (u64)sieve_block(row_count);
@@ -778,7 +851,11 @@ hipError_t launch_sieve(const KParams& p, uint32_t variant, hipStream_t stream) 
     if (!variant_fits(variant, p.capacity)) return hipErrorInvalidValue;
     constexpr int kCplx = F_CPLX, kKec = F_CPLX | F_KECCAK, kAll = F_CPLX | F_KECCAK | F_EVM;
     constexpr int kTab = kAll | F_TABLE;
-    if (variant >= kFirstTableVariant && !p.tables) return hipErrorInvalidValue;
+    if (variant >= kFirstTableVariant && variant != kSpillVariant && !p.tables)
+        return hipErrorInvalidValue;
+    // (a spilling tape with a lookup is refused without tables by the C-ABI, like a table tape)
+    if (variant == kSpillVariant && (!p.spill || !p.spill_slots)) return hipErrorInvalidValue;
+    constexpr int kSpill = kTab | F_SPILL;
     switch (variant) {
         case 0: return launch_variant<MH_NR_SMALL, 0>(p, stream);
         case 1: return launch_variant<MH_NR_SMALL, kCplx>(p, stream);
@@ -795,6 +872,7 @@ hipError_t launch_sieve(const KParams& p, uint32_t variant, hipStream_t stream) 
         case 12: return launch_variant<MH_NR_SMALL, kTab>(p, stream);
         case 13: return launch_variant<MH_NR_MID, kTab>(p, stream);
         case 14: return launch_variant<MH_NR_MAX, kTab>(p, stream);
+        case 15: return launch_variant<MH_NR_MAX, kSpill>(p, stream);
         default: return hipErrorInvalidValue;
     }
 }
@@ -820,6 +898,8 @@ hipError_t launch_sieve_batch(const KParams* segs, const batch::BlockEntry* bloc
         case 12: return launch_batch_variant<MH_NR_SMALL, kTab>(segs, blocks, n_blocks, stream);
         case 13: return launch_batch_variant<MH_NR_MID, kTab>(segs, blocks, n_blocks, stream);
         case 14: return launch_batch_variant<MH_NR_MAX, kTab>(segs, blocks, n_blocks, stream);
+        case 15:  // every segment carries the launch's spill region and slot count
+            return launch_batch_variant<MH_NR_MAX, kTab | F_SPILL>(segs, blocks, n_blocks, stream);
         default: return hipErrorInvalidValue;
     }
 }

@@ -22,14 +22,16 @@
 namespace mh {
 namespace values {
 
-constexpr uint32_t kVariants = 15;    // kernels.h kNumVariants: 0..11 table-free, 12..14 table
+constexpr uint32_t kVariants = 15;    // without spill code: 0..11 table-free, 12..14 table
+constexpr uint32_t kSpillVariant = 15;  // kernels.h kSpillVariant: the tapes that spill, after them
+constexpr uint32_t kAllVariants = 16;   // kernels.h kNumVariants
 constexpr uint32_t kJobsMax = 256;    // MH_VALUES_JOBS_MAX
 constexpr uint32_t kMinBlocks = 256;  // launch_block's target: a workgroup per CU
 
 // What the planner needs of one job: its id list and the variant of every listed id.
 struct JobShape {
     const uint32_t* ids = nullptr;
-    const uint32_t* variants = nullptr;  // [n], each < kVariants
+    const uint32_t* variants = nullptr;  // [n], each < kAllVariants
     uint32_t n = 0;
 };
 
@@ -51,7 +53,7 @@ struct Plan {
     std::vector<uint32_t> job_first;  // [n_jobs + 1] job j's slots are [job_first[j], job_first[j + 1])
     std::vector<Segment> segments;    // job-major, variants ascending inside a job
     std::vector<batch::BlockEntry> blocks;  // {segment, row block 0, tape slice, slices}
-    std::vector<Launch> launches;     // variants ascending, at most kVariants
+    std::vector<Launch> launches;     // variants ascending, at most kAllVariants
 };
 
 inline Plan plan(const JobShape* jobs, uint32_t n_jobs) {
@@ -61,7 +63,7 @@ inline Plan plan(const JobShape* jobs, uint32_t n_jobs) {
     for (uint32_t j = 0; j < n_jobs; ++j) total += jobs[j].n;
     p.ids.reserve(total);
     p.pos.reserve(total);
-    uint32_t segs_of[kVariants] = {};
+    uint32_t segs_of[kAllVariants] = {};
     std::vector<uint32_t> order;
     for (uint32_t j = 0; j < n_jobs; ++j) {
         const JobShape& s = jobs[j];
@@ -88,7 +90,7 @@ inline Plan plan(const JobShape* jobs, uint32_t n_jobs) {
     p.job_first[n_jobs] = (uint32_t)p.ids.size();
     // a segment is one row, so one row block: launch_block's rule over the whole launch splits
     // every segment's tape list until the chip has ~kMinBlocks workgroups
-    for (uint32_t v = 0; v < kVariants; ++v) {
+    for (uint32_t v = 0; v < kAllVariants; ++v) {
         if (!segs_of[v]) continue;
         const uint32_t want = segs_of[v] < kMinBlocks ? (kMinBlocks + segs_of[v] - 1) / segs_of[v] : 1;
         Launch l{v, (uint32_t)p.blocks.size(), 0};

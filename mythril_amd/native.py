@@ -57,6 +57,7 @@ SIGNATURES = {
     "mh_tapes_compile_wait": (C.c_int32, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_double)]),
     "mh_tapes_destroy": (C.c_int32, [_vp]),
     "mh_tapes_info": (C.c_int32, [_vp, _vp, C.c_uint32]),
+    "mh_tapes_spills": (C.c_int32, [_vp, _vp, C.c_uint32]),
     "mh_assign_create": (C.c_int32, [_vp, C.c_uint32, C.c_uint64, C.POINTER(_vp)]),
     "mh_assign_destroy": (C.c_int32, [_vp]),
     "mh_assign_upload": (C.c_int32, [_vp, _u32p, C.c_uint64, C.c_uint64]),
@@ -1044,6 +1045,12 @@ class CompiledTapes:
         _check(self.ctx.lib.mh_tapes_info(self.h, C.cast(arr, C.c_void_p), self.n_tapes))
         return [dict(n_nodes=x.n_nodes, n_insns=x.n_insns, n_regs=x.n_regs,
                      features=x.features, alg_ops=x.alg_ops) for x in arr[: self.n_tapes]]
+
+    def spills(self) -> np.ndarray:
+        """Spill slots per tape (0: the tape's live values fit the interpreter's registers)."""
+        out = np.zeros(max(self.n_tapes, 1), dtype=np.uint32)
+        _check(self.ctx.lib.mh_tapes_spills(self.h, _ptr(out), self.n_tapes))
+        return out[: self.n_tapes]
 
     def close(self) -> None:
         if self.h:

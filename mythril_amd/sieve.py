@@ -694,7 +694,7 @@ class Sieve:
         sizes = (0, 8, 32, 256)
         while True:
             try:
-                return self.ctx.compile(ts)
+                return self._count_spills(self.ctx.compile(ts))
             except native.Unsupported as e:
                 m = re.search(r"tape (\d+): register pressure", str(e))
                 if not m:
@@ -707,6 +707,15 @@ class Sieve:
                 ts.flat = None  # the tapes no longer lie back to back
                 k = "remat_%d" % sizes[level[t]]
                 self.stats.extra[k] = self.stats.extra.get(k, 0) + 1
+
+    def _count_spills(self, ct: native.CompiledTapes) -> native.CompiledTapes:
+        """Counts the tapes whose live values exceed the interpreter's registers: they compile
+        with spill code and run in the spill kernel (stats.extra["spilled_tapes"])."""
+        spills = getattr(ct, "spills", None)  # (a stand-in context's tapes have none)
+        n = int(np.count_nonzero(spills())) if spills is not None else 0
+        if n:
+            self.stats.extra["spilled_tapes"] = self.stats.extra.get("spilled_tapes", 0) + n
+        return ct
 
     @staticmethod
     def conjuncts(b: TapeBuilder, root: int) -> List[int]:
@@ -1210,6 +1219,7 @@ class Sieve:
                 except native.Unsupported:  # register pressure: Sieve.compile's retries
                     ct = None
                 if ct is not None:  # its own duration; the part the harvest did not hide
+                    self._count_spills(ct)
                     st.add("compile", ct.timing[1])
                     st.add("compile_wait", time.perf_counter() - t1)
             if ct is None:

@@ -8,6 +8,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "variants.h"
+
 namespace mh {
 namespace batch {
 
@@ -15,11 +17,11 @@ constexpr uint32_t kRowsPerBlock = 64;   // one-wave workgroups: the short-run s
 constexpr uint32_t kMaxRows = 4096;      // a job's rows at most (sieve_kernels.hip kShortRows)
 constexpr uint32_t kGenRowsPerBlock = 64;    // LDS generator forms (generate.hip kLdsRows)
 constexpr uint32_t kGenRowsPerBlockMem = 256;  // in-memory form (generate.hip kBlock)
-// NR class x feature class, then a fourth class of four: the table variants 12..14, which never
-// batch (a round's tapes hold no lookup), and the spill variant 15 (kernels.h kSpillVariant), whose
-// segments share one spill region indexed by the launch's workgroup
-constexpr uint32_t kInterpVariants = 16;
-constexpr uint32_t kClasses = 4;
+// NR class x feature class, then a fourth class of four (variants.h): the table variants 12..14,
+// which never batch (a round's tapes hold no lookup), and the spill variant 15, whose segments
+// share one spill region indexed by the launch's workgroup
+constexpr uint32_t kInterpVariants = kNumVariants;
+constexpr uint32_t kClasses = kNumClasses;
 constexpr uint32_t kForms = 3;
 constexpr uint32_t kMinBlocks = 256;     // launch_block's target: a workgroup per CU
 
@@ -40,7 +42,7 @@ inline GenForm gen_form(uint32_t n_cols, uint32_t span_words) {
 // What the planner needs of one job.
 struct JobShape {
     uint64_t count = 0;                      // rows, <= kMaxRows
-    // the job's tapes per interpreter bucket (kernels.h variant_of), inside its tape range
+    // the job's tapes per interpreter bucket (variants.h variant_of), inside its tape range
     uint32_t n_ids[kInterpVariants] = {};
     // the job runs its whole tape set: a register class's buckets are then one contiguous id range
     // (mh_run_async's merged short run), else every bucket is a range of its own
@@ -108,11 +110,11 @@ inline Plan plan(const JobShape* jobs, uint32_t n_jobs) {
             const JobShape& s = jobs[j];
             if (s.count == 0) continue;
             const uint64_t nb = (s.count + kRowsPerBlock - 1) / kRowsPerBlock;
-            for (uint32_t v = 4 * c; v < 4 * c + 4; ++v) {
+            for (uint32_t v = kClassVariants * c; v < kClassVariants * (c + 1); ++v) {
                 if (!s.n_ids[v]) continue;
                 Segment g{j, v, v, s.n_ids[v], 1};
                 if (s.whole)
-                    for (uint32_t u = v + 1; u < 4 * c + 4; ++u)
+                    for (uint32_t u = v + 1; u < kClassVariants * (c + 1); ++u)
                         if (s.n_ids[u]) {
                             g.last_bucket = u;
                             g.n_ids += s.n_ids[u];

@@ -25,6 +25,7 @@
 #include "domains.h"
 #include "jit.h"
 #include "kernels.h"
+#include "launch_plan.h"
 #include "values_plan.h"
 
 constexpr uint32_t kSideStreams = 3;  // with the ctx stream: GPU_MAX_HW_QUEUES (4) queues
@@ -161,19 +162,29 @@ const Rccl* rccl() {
 }  // namespace
 
 namespace {
-hipError_t ctx_dbuf(mh_ctx* c, size_t bytes, void** out) {
-    if (bytes > c->d_buf_bytes) {
-        if (c->d_buf) (void)hipFree(c->d_buf);
-        c->d_buf = nullptr;
-        c->d_buf_bytes = 0;
-        size_t n = 1 << 16;
-        while (n < bytes) n <<= 1;
-        hipError_t e = hipMalloc(&c->d_buf, n);
-        if (e != hipSuccess) return e;
-        c->d_buf_bytes = n;
-    }
-    *out = c->d_buf;
+// A grow-only buffer (*p of *have bytes, device or pinned host memory) made to hold `bytes`: kept
+// when it does, else freed and allocated anew at `least` bytes doubled until they suffice.  The
+// caller has made sure that nothing queued still uses the old block.
+template <class T>
+hipError_t grow_buf(T** p, size_t* have, size_t bytes, size_t least, bool pinned) {
+    if (bytes <= *have) return hipSuccess;
+    hipError_t e = !*p ? hipSuccess : pinned ? hipHostFree(*p) : hipFree(*p);
+    if (e != hipSuccess) return e;
+    *p = nullptr;
+    *have = 0;
+    size_t n = least;
+    while (n < bytes) n <<= 1;
+    void* q = nullptr;
+    e = pinned ? hipHostMalloc(&q, n, hipHostMallocDefault) : hipMalloc(&q, n);
+    if (e != hipSuccess) return e;
+    *p = static_cast<T*>(q);
+    *have = n;
     return hipSuccess;
+}
+hipError_t ctx_dbuf(mh_ctx* c, size_t bytes, void** out) {
+    const hipError_t e = grow_buf(&c->d_buf, &c->d_buf_bytes, bytes, 1 << 16, false);
+    *out = c->d_buf;
+    return e;
 }
 // smallest class 256 KiB: a query's whole tape set fits one block, so after the first query every
 // compile reuses a block (a hipMalloc of a size the process has not seen costs milliseconds)
@@ -215,18 +226,9 @@ void pool_free(mh_ctx* c, void* p) {
     c->pool_bytes += it->second;
 }
 hipError_t ctx_hbuf(mh_ctx* c, size_t bytes, void** out) {
-    if (bytes > c->h_buf_bytes) {
-        if (c->h_buf) (void)hipHostFree(c->h_buf);
-        c->h_buf = nullptr;
-        c->h_buf_bytes = 0;
-        size_t n = 1 << 16;
-        while (n < bytes) n <<= 1;
-        hipError_t e = hipHostMalloc(&c->h_buf, n, hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        c->h_buf_bytes = n;
-    }
+    const hipError_t e = grow_buf(&c->h_buf, &c->h_buf_bytes, bytes, 1 << 16, true);
     *out = c->h_buf;
-    return hipSuccess;
+    return e;
 }
 }  // namespace
 
@@ -239,11 +241,9 @@ struct mh_tapeset {
     mh_dev_tape* d_tapes = nullptr;
     uint32_t* d_consts = nullptr;
     std::vector<mh_tape_info> info;
-    // tapes bucketed by kernel variant (kernels.h variant_of): ascending tape ids per bucket,
-    // concatenated in d_ids; bucket v is [bucket_off[v], bucket_off[v+1])
-    uint32_t* d_ids = nullptr;
-    std::vector<uint32_t> ids;
-    uint32_t bucket_off[mh::kNumVariants + 1] = {};
+    // the tapes bucketed by kernel variant (launch_plan.h Buckets), and the id list on the device
+    mh::Buckets all;
+    uint32_t* d_all = nullptr;
     // host copy of the IR, for mh_tapes_jit
     std::vector<mh_node> h_nodes;
     std::vector<uint64_t> h_offs;
@@ -261,9 +261,8 @@ struct mh_tapeset {
     std::vector<JitMod> jit;
     std::vector<uint8_t> jitted;
     bool has_jit = false;
-    uint32_t* d_ids_rest = nullptr;
-    std::vector<uint32_t> ids_rest;
-    uint32_t bucket_off_rest[mh::kNumVariants + 1] = {};
+    mh::Buckets rest;
+    uint32_t* d_rest = nullptr;
     mh_jit_info jinfo{};
     uint64_t code_id = 0;   // mh::jit::code_id of the count kernels' module texts
     // conjunct-parallel short runs (mh_run_async): a long tape's root conjunction cut into parts
@@ -271,10 +270,9 @@ struct mh_tapeset {
     // in the order of their tapes) and bucketed like the tapes; the buckets without the split
     // tapes; per split tape, ascending: (tape, first part id, parts)
     uint32_t n_parts = 0;
-    std::vector<uint32_t> ids_unsplit, part_ids, part_parent, split_tab;
-    uint32_t bucket_off_unsplit[mh::kNumVariants + 1] = {};
-    uint32_t bucket_off_parts[mh::kNumVariants + 1] = {};
-    uint32_t *d_ids_unsplit = nullptr, *d_part_ids = nullptr, *d_split = nullptr;
+    mh::Buckets unsplit, parts;
+    std::vector<uint32_t> split_tab;
+    uint32_t *d_unsplit = nullptr, *d_parts = nullptr, *d_split = nullptr;
     // table lookups (MH_OP_LOOKUP): a tape that runs one (F_TABLE) makes the set runnable by
     // mh_eval_values_tables only; the (table id, key words) pairs the tapes' nodes name
     bool has_tables = false;
@@ -415,47 +413,14 @@ int32_t check_tables(const mh_ctx* ctx, const mh_tapeset* ts, const mh_tables* t
 // The batched entry points' pinned staging area and device block (mh_ctx::h_batch / d_batch),
 // grown to `bytes`: a submission goes up in one copy.
 int32_t ctx_batch_bufs(mh_ctx* ctx, size_t bytes) {
-    size_t n = 1 << 16;
-    while (n < bytes) n <<= 1;
-    if (bytes > ctx->h_batch_bytes) {
-        if (ctx->h_batch) MH_HIP(hipHostFree(ctx->h_batch));
-        ctx->h_batch = nullptr;
-        ctx->h_batch_bytes = 0;
-        MH_HIP(hipHostMalloc(&ctx->h_batch, n, hipHostMallocDefault));
-        ctx->h_batch_bytes = n;
-    }
-    if (bytes > ctx->d_batch_bytes) {
-        if (ctx->d_batch) MH_HIP(hipFree(ctx->d_batch));
-        ctx->d_batch = nullptr;
-        ctx->d_batch_bytes = 0;
-        MH_HIP(hipMalloc(&ctx->d_batch, n));
-        ctx->d_batch_bytes = n;
-    }
+    MH_HIP(grow_buf(&ctx->h_batch, &ctx->h_batch_bytes, bytes, 1 << 16, true));
+    MH_HIP(grow_buf(&ctx->d_batch, &ctx->d_batch_bytes, bytes, 1 << 16, false));
     return MH_OK;
 }
 
-// The regions the spilling launches of one call take out of the ctx's spill memory: take() per
-// launch while the call is planned, spill_reserve() once before anything is queued, at() when the
-// launch's KParams are made.
-struct SpillPlan {
-    uint64_t words = 0;
-    // the launch's region (its offset in words) for `waves` waves of `slots` slots each
-    uint64_t take(uint64_t waves, uint32_t slots) {
-        const uint64_t off = words;
-        words += mh::spill_words(waves, slots);
-        return off;
-    }
-};
-
-// the most spill slots a tape of ids [b, e) uses (a launch's KParams::spill_slots)
-uint32_t max_spills(const mh_tapeset* ts, const uint32_t* b, const uint32_t* e) {
-    uint32_t m = 0;
-    for (; b != e; ++b) m = std::max(m, ts->spills[*b]);
-    return m;
-}
-
-// Makes the ctx's spill memory hold `words` words.  Called before a call queues anything: a call
-// whose spill areas exceed the cap (256 MiB; MH_SPILL_CAP_MB for experiments) is refused whole.
+// Makes the ctx's spill memory hold `words` words: a call's mh::SpillPlan (launch_plan.h), the
+// regions its spilling launches took while it was planned.  Called before a call queues anything: a
+// call whose spill areas exceed the cap (256 MiB; MH_SPILL_CAP_MB for experiments) is refused whole.
 // The memory grows only here, after everything queued on the ctx's streams has finished, so no
 // launch can still be using the block that is freed.
 int32_t spill_reserve(mh_ctx* ctx, uint64_t words) {
@@ -475,16 +440,61 @@ int32_t spill_reserve(mh_ctx* ctx, uint64_t words) {
     MH_HIP(hipStreamSynchronize(ctx->stream));
     for (hipStream_t sd : ctx->side)
         if (sd) MH_HIP(hipStreamSynchronize(sd));
-    if (ctx->d_spill) MH_HIP(hipFree(ctx->d_spill));
-    ctx->d_spill = nullptr;
-    ctx->spill_bytes = 0;
-    size_t n = (size_t)1 << 20;
-    while (n < bytes) n <<= 1;
-    hipError_t e = hipMalloc(&ctx->d_spill, n);
+    const hipError_t e = grow_buf(&ctx->d_spill, &ctx->spill_bytes, bytes, (size_t)1 << 20, false);
     if (e != hipSuccess)
         return set_err(MH_E_NOMEM, std::string("spill memory: ") + hipGetErrorString(e));
-    ctx->spill_bytes = n;
     return MH_OK;
+}
+
+// a planned launch's spill fields (mh::plan_launches) in its KParams
+void bind_spill(mh::KParams& q, const mh_ctx* ctx, const mh::Launch& l) {
+    if (l.variant != mh::kSpillVariant) return;
+    q.spill = ctx->d_spill + l.spill_off;
+    q.spill_slots = l.spill_slots;
+}
+
+inline uint32_t seg_variant(const mh::batch::Segment& sg) { return sg.last_bucket; }
+inline uint32_t seg_variant(const mh::values::Segment& sg) { return sg.variant; }
+// The spill tail of a batched submission (mh_query_round_many, mh_eval_values_jobs), after the
+// segments' KParams are made and before anything is queued.  At most one launch runs the spill
+// variant (a register class of its own); its region is sized by its workgroups (one wave each, the
+// area picked by the launch's workgroup index) times the most slots a tape of its segments uses,
+// and every such segment names that region and slot count.  seg_tapes(sg) = the segment's tape
+// set and its first id in the host's id list.
+template <class Plan, class SegTapes>
+int32_t batch_spill(mh_ctx* ctx, const Plan& plan, mh::KParams* h_seg, SegTapes seg_tapes) {
+    uint32_t slots = 0;
+    for (const auto& sg : plan.segments)
+        if (seg_variant(sg) == mh::kSpillVariant) {
+            const std::pair<const mh_tapeset*, const uint32_t*> t = seg_tapes(sg);
+            for (uint32_t i = 0; i < sg.n_ids; ++i)
+                slots = std::max(slots, t.first->spills[t.second[i]]);
+        }
+    mh::SpillPlan spill;
+    for (const auto& l : plan.launches)
+        if (l.variant == mh::kSpillVariant) (void)spill.take(l.count, slots);
+    if (int32_t r = spill_reserve(ctx, spill.words)) return r;
+    for (size_t si = 0; si < plan.segments.size(); ++si)
+        if (seg_variant(plan.segments[si]) == mh::kSpillVariant) {
+            h_seg[si].spill = ctx->d_spill;
+            h_seg[si].spill_slots = slots;
+        }
+    return MH_OK;
+}
+
+// One timed span of launches on the ctx stream (mh_ctx_kernel_time sums them): nothing unless
+// timing is on
+hipError_t span_begin(mh_ctx* ctx) {
+    if (!ctx->timing) return hipSuccess;
+    std::pair<hipEvent_t, hipEvent_t> sp{nullptr, nullptr};
+    hipError_t e = hipEventCreate(&sp.first);
+    if (e == hipSuccess) e = hipEventCreate(&sp.second);
+    if (e != hipSuccess) return e;
+    ctx->spans.push_back(sp);
+    return hipEventRecord(sp.first, ctx->stream);
+}
+hipError_t span_end(mh_ctx* ctx) {
+    return ctx->timing ? hipEventRecord(ctx->spans.back().second, ctx->stream) : hipSuccess;
 }
 
 mh::KParams make_params(const mh_tapeset* ts, uint32_t tape_first, const mh_assign* as,
@@ -555,7 +565,8 @@ int32_t launch_jit(mh_ctx* ctx, const mh_tapeset* ts, const mh_assign* as, uint6
 
 static int32_t eval_values_rows(mh_ctx* ctx, const mh_tapeset* ts, const mh_tables* tables,
                                 const uint32_t* tapes, uint32_t n, const mh_assign* as,
-                                uint64_t row, uint64_t row_count, uint32_t* out, const char* who);
+                                uint64_t row, uint64_t row_count, uint32_t* out, const char* who,
+                                bool single);
 
 extern "C" {
 
@@ -818,10 +829,9 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
     std::vector<mh_dev_tape> heads(n_tapes);
     std::vector<mh_tape_info> info(n_tapes);
     std::vector<uint32_t> spills(n_tapes, 0);  // slots per tape, then per part
-    std::vector<uint32_t> ids, bucket_off(mh::kNumVariants + 1, 0);
-    // conjunct-parallel parts (mh_tapeset): heads n_tapes.. and their buckets
-    std::vector<uint32_t> ids_unsplit, part_ids, part_parent, split_tab;
-    uint32_t off_unsplit[mh::kNumVariants + 1] = {}, off_parts[mh::kNumVariants + 1] = {};
+    // the buckets of the tapes, and of the conjunct-parallel parts (mh_tapeset): heads n_tapes..
+    mh::Buckets bk_all, bk_unsplit, bk_parts;
+    std::vector<uint32_t> split_tab;
     try {
         std::vector<std::vector<uint32_t>> tw(n_tapes);
         static const bool use_cache = [] {
@@ -913,7 +923,6 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
                 continue;
             }
             split_tab.insert(split_tab.end(), {t, n_tapes + (uint32_t)p0, (uint32_t)parts.size()});
-            for (size_t i = p0; i < pw.size(); ++i) part_parent.push_back(t);
         }
         // bucket by kernel variant; instruction words laid out bucket by bucket (ascending tape
         // id inside a bucket) so that any run of consecutive bucket entries is one contiguous
@@ -921,36 +930,23 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
         // after the tapes, likewise
         std::vector<char> is_split(n_tapes, 0);
         for (size_t i = 0; i < split_tab.size(); i += 3) is_split[split_tab[i]] = 1;
-        std::vector<std::vector<uint32_t>> bucket(mh::kNumVariants);
-        for (uint32_t t = 0; t < n_tapes; ++t)
-            bucket[mh::variant_of(info[t].n_regs, info[t].features)].push_back(t);
-        for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
-            bucket_off[v] = (uint32_t)ids.size();
-            off_unsplit[v] = (uint32_t)ids_unsplit.size();
-            for (uint32_t t : bucket[v]) {
-                heads[t].insn_off = (uint32_t)(words.size() / 2);
-                words.insert(words.end(), tw[t].begin(), tw[t].end());
-                ids.push_back(t);
-                if (!is_split[t]) ids_unsplit.push_back(t);
-            }
-        }
-        bucket_off[mh::kNumVariants] = (uint32_t)ids.size();
-        off_unsplit[mh::kNumVariants] = (uint32_t)ids_unsplit.size();
-        std::vector<std::vector<uint32_t>> pbucket(mh::kNumVariants);
-        for (uint32_t i = 0; i < (uint32_t)pw.size(); ++i)
-            pbucket[mh::variant_of(pinfo[i].n_regs, pinfo[i].features)].push_back(i);
-        heads.resize(n_tapes + pw.size());
-        for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
-            off_parts[v] = (uint32_t)part_ids.size();
-            for (uint32_t i : pbucket[v]) {
-                heads[n_tapes + i] = pheads[i];
-                heads[n_tapes + i].insn_off = (uint32_t)(words.size() / 2);
-                words.insert(words.end(), pw[i].begin(), pw[i].end());
-                part_ids.push_back(n_tapes + i);
-            }
-        }
-        off_parts[mh::kNumVariants] = (uint32_t)part_ids.size();
+        heads.insert(heads.end(), pheads.begin(), pheads.end());
         spills.insert(spills.end(), pspills.begin(), pspills.end());
+        const auto variant = [&](uint32_t t) {  // of a tape, or of the part with id t
+            const mh_tape_info& ti = t < n_tapes ? info[t] : pinfo[t - n_tapes];
+            return mh::variant_of(ti.n_regs, ti.features);
+        };
+        const auto every = [](uint32_t) { return true; };
+        bk_all = mh::Buckets::build(n_tapes, 0, variant, every);
+        bk_unsplit = mh::Buckets::build(n_tapes, 0, variant, [&](uint32_t t) { return !is_split[t]; });
+        bk_parts = mh::Buckets::build((uint32_t)pw.size(), n_tapes,
+                                      [&](uint32_t i) { return variant(n_tapes + i); }, every);
+        for (const mh::Buckets* bk : {&bk_all, &bk_parts})
+            for (uint32_t t : bk->ids) {
+                const std::vector<uint32_t>& w = t < n_tapes ? tw[t] : pw[t - n_tapes];
+                heads[t].insn_off = (uint32_t)(words.size() / 2);
+                words.insert(words.end(), w.begin(), w.end());
+            }
     } catch (const std::bad_alloc&) {
         return set_err(MH_E_NOMEM, "host allocation during compile");
     }
@@ -975,33 +971,27 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
         mh_tapes_destroy(ts);
         return set_err(MH_E_NOMEM, "host copy of the tapes");
     }
-    ts->ids = std::move(ids);
-    for (uint32_t v = 0; v <= mh::kNumVariants; ++v) {
-        ts->bucket_off[v] = bucket_off[v];
-        ts->bucket_off_unsplit[v] = off_unsplit[v];
-        ts->bucket_off_parts[v] = off_parts[v];
-    }
+    ts->all = std::move(bk_all);
+    ts->unsplit = std::move(bk_unsplit);
+    ts->parts = std::move(bk_parts);
     ts->info = std::move(info);
     ts->spills = std::move(spills);
     for (const mh_tape_info& ti : ts->info) ts->has_tables |= (ti.features & F_TABLE) != 0;
     for (uint32_t t = 0; t < n_tapes; ++t)
         mh::tape_lookups(nodes + tape_offsets[t], (size_t)(tape_offsets[t + 1] - tape_offsets[t]),
                          ts->lookups);
-    ts->n_parts = (uint32_t)part_parent.size();
-    ts->ids_unsplit = std::move(ids_unsplit);
-    ts->part_ids = std::move(part_ids);
-    ts->part_parent = std::move(part_parent);
+    ts->n_parts = (uint32_t)ts->parts.ids.size();
     ts->split_tab = std::move(split_tab);
     // one device block and one async copy from pinned staging (a query compiles a tape set per
     // call: four synchronous pageable copies cost more than the kernels they feed)
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     auto b_u32 = [](const std::vector<uint32_t>& v) { return std::max<size_t>(1, v.size()) * 4; };
-    const size_t b_insns = words.size() * sizeof(uint32_t), b_ids = b_u32(ts->ids),
+    const size_t b_insns = words.size() * sizeof(uint32_t), b_ids = b_u32(ts->all.ids),
                  b_tapes = std::max<size_t>(1, heads.size()) * sizeof(mh_dev_tape),
                  b_consts = dconsts.size() * sizeof(uint32_t);
     const size_t o_ids = al(b_insns), o_tapes = o_ids + al(b_ids), o_consts = o_tapes + al(b_tapes),
-                 o_unsplit = o_consts + al(b_consts), o_parts = o_unsplit + al(b_u32(ts->ids_unsplit)),
-                 o_split = o_parts + al(b_u32(ts->part_ids)),
+                 o_unsplit = o_consts + al(b_consts), o_parts = o_unsplit + al(b_u32(ts->unsplit.ids)),
+                 o_split = o_parts + al(b_u32(ts->parts.ids)),
                  total = o_split + al(b_u32(ts->split_tab));
     hipError_t e = pool_alloc(ctx, (char**)&ts->d_block, total);
     if (e == hipSuccess && ctx->stage_pending) {
@@ -1021,22 +1011,22 @@ int32_t mh_tapes_compile(mh_ctx* ctx, const mh_node* nodes, const uint64_t* tape
     if (e == hipSuccess) {
         char* h = (char*)ctx->h_stage;
         std::memcpy(h, words.data(), b_insns);
-        if (!ts->ids.empty()) std::memcpy(h + o_ids, ts->ids.data(), ts->ids.size() * sizeof(uint32_t));
         if (!heads.empty()) std::memcpy(h + o_tapes, heads.data(), heads.size() * sizeof(mh_dev_tape));
         std::memcpy(h + o_consts, dconsts.data(), b_consts);
         auto put = [&](size_t o, const std::vector<uint32_t>& v) {
             if (!v.empty()) std::memcpy(h + o, v.data(), v.size() * sizeof(uint32_t));
         };
-        put(o_unsplit, ts->ids_unsplit);
-        put(o_parts, ts->part_ids);
+        put(o_ids, ts->all.ids);
+        put(o_unsplit, ts->unsplit.ids);
+        put(o_parts, ts->parts.ids);
         put(o_split, ts->split_tab);
         char* d = (char*)ts->d_block;
         ts->d_insns = (uint2*)d;
-        ts->d_ids = (uint32_t*)(d + o_ids);
+        ts->d_all = (uint32_t*)(d + o_ids);
         ts->d_tapes = (mh_dev_tape*)(d + o_tapes);
         ts->d_consts = (uint32_t*)(d + o_consts);
-        ts->d_ids_unsplit = (uint32_t*)(d + o_unsplit);
-        ts->d_part_ids = (uint32_t*)(d + o_parts);
+        ts->d_unsplit = (uint32_t*)(d + o_unsplit);
+        ts->d_parts = (uint32_t*)(d + o_parts);
         ts->d_split = (uint32_t*)(d + o_split);
         e = hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(ctx->stage_ev, ctx->stream);
@@ -1064,7 +1054,7 @@ int32_t mh_tapes_destroy(mh_tapeset* ts) {
     // kernels of this set may still run on the ctx stream: finish them before the blocks go back
     if (ts->ctx->stream) (void)hipStreamSynchronize(ts->ctx->stream);
     pool_free(ts->ctx, ts->d_block);
-    if (ts->d_ids_rest) (void)hipFree(ts->d_ids_rest);
+    if (ts->d_rest) (void)hipFree(ts->d_rest);
     for (auto& j : ts->jit) {
         if (j.mod) (void)hipModuleUnload(j.mod);
         if (j.vmod) (void)hipModuleUnload(j.vmod);
@@ -1518,24 +1508,11 @@ int32_t mh_run_async(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first, uin
         return e ? std::strtoull(e, nullptr, 10) : 65536ull;
     }();
     const bool split = !use_jit && ts->n_parts && row_count <= split_rows;
-    const std::vector<uint32_t>& ids = use_jit ? ts->ids_rest : split ? ts->ids_unsplit : ts->ids;
-    const uint32_t* boff = use_jit ? ts->bucket_off_rest
-                                   : split ? ts->bucket_off_unsplit : ts->bucket_off;
-    uint32_t* d_ids = use_jit ? ts->d_ids_rest : split ? ts->d_ids_unsplit : ts->d_ids;
-    // the interpreter's tapes of each kernel-variant bucket inside the requested range
-    const uint32_t *lo[mh::kNumVariants], *hi[mh::kNumVariants];
-    for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
-        const uint32_t* b = ids.data() + boff[v];
-        const uint32_t* e = ids.data() + boff[v + 1];
-        lo[v] = std::lower_bound(b, e, tape_first);
-        hi[v] = std::lower_bound(lo[v], e, tape_first + tape_count);
-        // refused before anything is launched
-        if (hi[v] != lo[v] && !mh::variant_fits(v, p.capacity)) return refuse_capacity(p.capacity);
-    }
-    // the split tapes inside the range (split_tab ascends by tape, part ids with it) and their
-    // parts per bucket
+    const mh::Buckets& ids = use_jit ? ts->rest : split ? ts->unsplit : ts->all;
+    const uint32_t* d_ids = use_jit ? ts->d_rest : split ? ts->d_unsplit : ts->d_all;
+    // the split tapes inside the range (split_tab ascends by tape, part ids with it): their parts
+    // are the ids [part_lo, part_hi)
     uint32_t s_lo = 0, s_hi = 0, part_lo = 0, part_hi = 0;
-    const uint32_t *plo[mh::kNumVariants] = {}, *phi[mh::kNumVariants] = {};
     if (split) {
         const uint32_t n_split = (uint32_t)ts->split_tab.size() / 3;
         while (s_lo < n_split && ts->split_tab[3 * s_lo] < tape_first) ++s_lo;
@@ -1545,82 +1522,37 @@ int32_t mh_run_async(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first, uin
             part_lo = ts->split_tab[3 * s_lo + 1];
             part_hi = ts->split_tab[3 * (s_hi - 1) + 1] + ts->split_tab[3 * (s_hi - 1) + 2];
         }
-        for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
-            const uint32_t* b = ts->part_ids.data() + ts->bucket_off_parts[v];
-            const uint32_t* e = ts->part_ids.data() + ts->bucket_off_parts[v + 1];
-            plo[v] = std::lower_bound(b, e, part_lo);
-            phi[v] = std::lower_bound(plo[v], e, part_hi);
-            if (phi[v] != plo[v] && !mh::variant_fits(v, p.capacity)) return refuse_capacity(p.capacity);
-        }
     }
-    // the spilling tapes' launches (whole tapes, parts): a region each, which may overlap on the
-    // side streams; sized and refused before anything is queued
-    SpillPlan spill;
-    uint64_t spill_off[2] = {0, 0};
-    uint32_t spill_slots[2] = {0, 0};
-    for (int part = 0; part < 2; ++part) {
-        const uint32_t* b = part ? plo[mh::kSpillVariant] : lo[mh::kSpillVariant];
-        const uint32_t* e = part ? phi[mh::kSpillVariant] : hi[mh::kSpillVariant];
-        if (b == e || row_count == 0) continue;
-        spill_slots[part] = max_spills(ts, b, e);
-        spill_off[part] = spill.take(
-            mh::sieve_launch_waves(row_count, (uint32_t)(e - b), part != 0), spill_slots[part]);
-    }
+    // one launch per kernel-variant bucket; a short run (a query's guided first round) over the
+    // whole set is one launch per register class instead (launch_plan.h plan_launches)
+    static const uint64_t merge_rows = [] {
+        const char* e = std::getenv("MH_MERGE_ROWS");
+        return e ? std::strtoull(e, nullptr, 10) : 4096ull;
+    }();
+    const bool merge = !use_jit && row_count <= merge_rows && tape_first == 0 &&
+                       tape_count == ts->n_tapes;
+    // the launches of the whole tapes [0] and of the parts [1] (none unless `split`), a region of
+    // spill memory for each that spills (they may overlap on the side streams): refused, and the
+    // memory sized, before anything is queued
+    mh::SpillPlan spill;
+    const mh::LaunchPlan plans[2] = {
+        mh::plan_launches(ids, tape_first, tape_count, row_count, merge, false, p.capacity,
+                          ts->spills.data(), spill, mh::sieve_launch_waves),
+        mh::plan_launches(ts->parts, part_lo, part_hi - part_lo, row_count, merge, true,
+                          p.capacity, ts->spills.data(), spill, mh::sieve_launch_waves)};
+    if (plans[0].misfit >= 0 || plans[1].misfit >= 0) return refuse_capacity(p.capacity);
     if (int32_t r = spill_reserve(ctx, spill.words)) return r;
     const uint64_t mask_stride = mh::sieve_mask_stride(row_count);
-    if (part_hi > part_lo) {
-        const size_t need = (size_t)(part_hi - part_lo) * mask_stride * sizeof(unsigned long long);
-        if (need > ctx->masks_bytes) {
-            if (ctx->d_masks) MH_HIP(hipFree(ctx->d_masks));
-            ctx->d_masks = nullptr;
-            ctx->masks_bytes = 0;
-            size_t n = 1 << 16;
-            while (n < need) n <<= 1;
-            MH_HIP(hipMalloc(&ctx->d_masks, n));
-            ctx->masks_bytes = n;
-        }
-    }
-    std::pair<hipEvent_t, hipEvent_t> sp{nullptr, nullptr};
-    if (ctx->timing) {
-        MH_HIP(hipEventCreate(&sp.first));
-        MH_HIP(hipEventCreate(&sp.second));
-        ctx->spans.push_back(sp);
-        MH_HIP(hipEventRecord(sp.first, ctx->stream));
-    }
+    MH_HIP(grow_buf(&ctx->d_masks, &ctx->masks_bytes,
+                    (size_t)(part_hi - part_lo) * mask_stride * sizeof(unsigned long long),
+                    1 << 16, false));
+    MH_HIP(span_begin(ctx));
     if (use_jit && row_count) {
         if (int32_t r = launch_jit(ctx, ts, as, row_first, row_count, index_base, mode,
                                    d_first_hit, d_hit_count, nullptr))
             return r;
     }
-    // one launch per kernel-variant bucket; a short run (a query's guided first round) is one
-    // launch per register class instead: the feature sets nest (kernels.h variant_of: a kernel
-    // with more handlers runs a tape that needs fewer), the register classes do not (a tape's
-    // instruction words address its class's registers), and a class's buckets are consecutive
-    // in the id list, which is laid out in the order of the tapes' words
-    static const uint64_t merge_rows = [] {
-        const char* e = std::getenv("MH_MERGE_ROWS");
-        return e ? std::strtoull(e, nullptr, 10) : 4096ull;
-    }();
-    // (over the whole set only: every bucket is then whole, so a class's buckets are one range)
-    const bool merge = !use_jit && row_count <= merge_rows && tape_first == 0 &&
-                       tape_count == ts->n_tapes;
-    struct Launch { const uint32_t *b, *e; uint32_t variant; bool part; };
-    Launch launches[2 * mh::kNumVariants];
-    uint32_t n_launch = 0;
-    for (int part = 0; part < 2; ++part) {
-        const uint32_t* const* L = part ? plo : lo;
-        const uint32_t* const* H = part ? phi : hi;
-        if (part && !split) break;
-        for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
-            if (H[v] == L[v]) continue;
-            uint32_t last = v;  // with merging: the class's last nonempty bucket, L[v]..H[last]
-            if (merge)
-                for (uint32_t u = v + 1; u < (v / 4 + 1) * 4; ++u)
-                    if (H[u] != L[u]) last = u;
-            launches[n_launch++] = Launch{L[v], H[last], last, part != 0};
-            v = last;
-        }
-    }
+    const uint32_t n_launch = plans[0].n + plans[1].n;
     // a short run's launches overlap on the side streams (made with the ctx when the fan-out
     // is on); the results they write are disjoint (per tape / per part), and the join puts
     // everything after them back in `stream`'s order
@@ -1631,25 +1563,22 @@ int32_t mh_run_async(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first, uin
         for (uint32_t i = 0; i < n_side; ++i) MH_HIP(hipStreamWaitEvent(ctx->side[i], ctx->fork_ev, 0));
     }
     for (uint32_t i = 0; i < n_launch; ++i) {
+        const bool part = i >= plans[0].n;
+        const mh::Launch& l = part ? plans[1].launches[i - plans[0].n] : plans[0].launches[i];
         mh::KParams q = p;
-        if (launches[i].part) {  // wave masks instead of results
-            q.tape_ids = ts->d_part_ids + (launches[i].b - ts->part_ids.data());
+        if (part) {  // wave masks instead of results
             q.masks = ctx->d_masks;
             q.mask_base = part_lo;
             q.mask_stride = mask_stride;
             q.first_hit = nullptr;
             q.hit_count = nullptr;
-        } else {
-            q.tape_ids = d_ids + (launches[i].b - ids.data());
         }
-        q.n_ids = (uint32_t)(launches[i].e - launches[i].b);
-        if (launches[i].variant == mh::kSpillVariant) {
-            q.spill = ctx->d_spill + spill_off[launches[i].part];
-            q.spill_slots = spill_slots[launches[i].part];
-        }
+        q.tape_ids = (part ? ts->d_parts : d_ids) + l.first;
+        q.n_ids = l.count;
+        bind_spill(q, ctx, l);
         // launch 0 on the ctx stream, the others round-robin over the side streams
         hipStream_t s = n_side && i ? ctx->side[(i - 1) % n_side] : ctx->stream;
-        MH_HIP(mh::launch_sieve(q, launches[i].variant, s));
+        MH_HIP(mh::launch_sieve(q, l.variant, s));
     }
     for (uint32_t i = 0; i < n_side; ++i) {
         MH_HIP(hipEventRecord(ctx->join_ev[i], ctx->side[i]));
@@ -1659,7 +1588,7 @@ int32_t mh_run_async(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first, uin
         MH_HIP(mh::launch_combine(ctx->d_masks, mask_stride, ts->d_split + 3 * s_lo, s_hi - s_lo,
                                   part_lo, tape_first, index_base + row_first, p.first_hit,
                                   p.hit_count, ctx->stream));
-    if (ctx->timing) MH_HIP(hipEventRecord(sp.second, ctx->stream));
+    MH_HIP(span_end(ctx));
     return MH_OK;
 }
 
@@ -1825,7 +1754,7 @@ int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jo
     };
     struct JobPlan {
         GuideLayout L;
-        const uint32_t *lo[mh::batch::kInterpVariants], *hi[mh::batch::kInterpVariants];
+        mh::Buckets::Range in[mh::kNumVariants];  // the job's tapes per bucket
         size_t guide_off = 0, res_off = 0;  // words of the device block / bytes of the results
     };
     std::vector<JobPlan> jp(n_jobs);
@@ -1855,18 +1784,15 @@ int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jo
             return job_err(i, MH_E_INVALID, "rows_out null or n_cols beyond the buffer's columns");
         if (int32_t r = refuse_tables(j.ts)) return job_err(i, r, g_err);
         if (int32_t r = check_guide(j.as, j.guide, &jp[i].L)) return job_err(i, r, g_err);
-        // the job's tapes per interpreter bucket: whole tapes (ts->ids), never split parts
+        // the job's tapes per interpreter bucket: whole tapes (ts->all), never split parts
         mh::batch::JobShape& sh = shapes[i];
         sh.count = j.count;
         sh.whole = j.tape_first == 0 && j.tape_count == j.ts->n_tapes;
         sh.gen_n_cols = jp[i].L.nc;
         sh.gen_span_words = (uint32_t)(jp[i].L.o_eval - jp[i].L.o_prob);
-        for (uint32_t v = 0; v < mh::batch::kInterpVariants; ++v) {
-            const uint32_t* b = j.ts->ids.data() + j.ts->bucket_off[v];
-            const uint32_t* e = j.ts->ids.data() + j.ts->bucket_off[v + 1];
-            jp[i].lo[v] = std::lower_bound(b, e, j.tape_first);
-            jp[i].hi[v] = std::lower_bound(jp[i].lo[v], e, j.tape_first + j.tape_count);
-            sh.n_ids[v] = (uint32_t)(jp[i].hi[v] - jp[i].lo[v]);
+        for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
+            jp[i].in[v] = j.ts->all.range(v, j.tape_first, j.tape_count);
+            sh.n_ids[v] = jp[i].in[v].count;
         }
         jp[i].res_off = res_bytes;
         res_bytes += 2 * (size_t)j.tape_count * sizeof(uint64_t) +
@@ -1887,18 +1813,6 @@ int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jo
                 return job_err(job, MH_E_UNSUPPORTED, g_err);
             }
         }
-    // the spilling tapes' launch (at most one: the spill variant is a register class of its own):
-    // every segment of it names the launch's region and its slot count, the most over the
-    // launch's tapes; a wave's area is picked by the launch's workgroup index
-    SpillPlan spill;
-    uint32_t spill_slots = 0;
-    for (const mh::batch::Segment& sg : plan.segments)
-        if (sg.last_bucket == mh::kSpillVariant) {
-            const uint32_t* lo = jp[sg.job].lo[sg.first_bucket];
-            spill_slots = std::max(spill_slots, max_spills(jobs[sg.job].ts, lo, lo + sg.n_ids));
-        }
-    for (const auto& l : plan.launches)
-        if (l.variant == mh::kSpillVariant) (void)spill.take(l.count, spill_slots);
     // the device block: segments' KParams | GenJob[] | ResultJob[] | block tables | guides
     const auto align = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_seg = 0;
@@ -1912,7 +1826,6 @@ int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jo
         up_bytes = align(up_bytes + jp[i].L.words * sizeof(uint32_t));
     }
     if (int32_t r = use_device(ctx)) return r;
-    if (int32_t r = spill_reserve(ctx, spill.words)) return r;
     if (int32_t r = ctx_batch_bufs(ctx, up_bytes)) return r;
     void* dres_v = nullptr;
     void* hres_v = nullptr;
@@ -1953,28 +1866,22 @@ int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jo
         unsigned long long* fh = reinterpret_cast<unsigned long long*>(dres + jp[sg.job].res_off);
         p.first_hit = fh;
         p.hit_count = fh + j.tape_count;
-        p.tape_ids = j.ts->d_ids + (jp[sg.job].lo[sg.first_bucket] - j.ts->ids.data());
+        p.tape_ids = j.ts->d_all + jp[sg.job].in[sg.first_bucket].first;
         p.n_ids = sg.n_ids;
-        if (sg.last_bucket == mh::kSpillVariant) {
-            p.spill = ctx->d_spill;
-            p.spill_slots = spill_slots;
-        }
         h_seg[si] = p;
     }
+    if (int32_t r = batch_spill(ctx, plan, h_seg, [&](const mh::batch::Segment& sg) {
+            const mh_tapeset* ts = jobs[sg.job].ts;
+            return std::make_pair(ts, ts->all.ids.data() + jp[sg.job].in[sg.first_bucket].first);
+        }))
+        return r;
     if (!plan.blocks.empty())
         std::memcpy(hb + o_blk, plan.blocks.data(),
                     plan.blocks.size() * sizeof(mh::batch::BlockEntry));
     if (!gplan.gen_blocks.empty())
         std::memcpy(hb + o_gblk, gplan.gen_blocks.data(),
                     gplan.gen_blocks.size() * sizeof(mh::batch::GenEntry));
-    // one span for the whole submission
-    std::pair<hipEvent_t, hipEvent_t> sp{nullptr, nullptr};
-    if (ctx->timing) {
-        MH_HIP(hipEventCreate(&sp.first));
-        MH_HIP(hipEventCreate(&sp.second));
-        ctx->spans.push_back(sp);
-        MH_HIP(hipEventRecord(sp.first, ctx->stream));
-    }
+    MH_HIP(span_begin(ctx));  // one span for the whole submission
     hipStream_t s = ctx->stream;
     hipError_t e = hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, s);
     const mh::GenJob* d_gen = reinterpret_cast<const mh::GenJob*>(db + o_gen);
@@ -1991,7 +1898,7 @@ int32_t mh_query_round_many(mh_ctx* ctx, const mh_round_job* jobs, uint32_t n_jo
             e = mh::launch_sieve_batch(reinterpret_cast<const mh::KParams*>(db + o_seg),
                                        d_blk + l.first, l.count, l.variant, s);
     if (e == hipSuccess && any_rows) e = mh::launch_witness_rows_batch(d_res, n_jobs, max_tc, s);
-    if (e == hipSuccess && ctx->timing) e = hipEventRecord(sp.second, s);
+    if (e == hipSuccess) e = span_end(ctx);
     if (e == hipSuccess && res_bytes)
         e = hipMemcpyAsync(hres_v, dres, res_bytes, hipMemcpyDeviceToHost, s);
     // the staging area is read by the queued copy: wait even after an error
@@ -2019,47 +1926,15 @@ int32_t mh_eval_values(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape, const m
         return r;
     if (!out && row_count) return set_err(MH_E_INVALID, "null out");
     if (int32_t r = refuse_tables(ts)) return r;
-    if (row_count == 0) return MH_OK;
-    if (int32_t r = use_device(ctx)) return r;
-    const uint32_t variant = mh::variant_of(ts->info[tape].n_regs, ts->info[tape].features);
-    if (!mh::variant_fits(variant, as->stride)) return refuse_capacity(as->stride);
-    SpillPlan spill;
-    if (variant == mh::kSpillVariant)
-        (void)spill.take(mh::sieve_launch_waves(row_count, 1, false), ts->spills[tape]);
-    if (int32_t r = spill_reserve(ctx, spill.words)) return r;
-    // the production sieve kernel in values mode, over a one-tape list
-    uint32_t* d = nullptr;
-    MH_HIP(hipMalloc(&d, (8 * row_count + 8) * sizeof(uint32_t)));
-    uint32_t* d_id = d + 8 * row_count;  // [0]: tape id, [2..5]: first_hit / hit_count
-    mh::KParams p = make_params(ts, tape, as, row_first, row_count, 0, MH_MODE_COUNT_ALL);
-    p.tape_ids = d_id;
-    p.n_ids = 1;
-    p.first_hit = reinterpret_cast<unsigned long long*>(d_id + 2);
-    p.hit_count = reinterpret_cast<unsigned long long*>(d_id + 4);
-    p.values_out = d;
-    if (variant == mh::kSpillVariant) {
-        p.spill = ctx->d_spill;
-        p.spill_slots = ts->spills[tape];
-    }
-    // copies on the ctx stream: the first use of the null stream creates a hardware queue
-    // (20.6 ms, profiles/r04x), which a query's first definitions evaluation paid
-    const uint32_t ids[8] = {tape, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0, 0};
-    hipError_t e = hipMemcpyAsync(d_id, ids, sizeof(ids), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = mh::launch_sieve(p, variant, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(out, d, 8 * row_count * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                           ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess)
-        return set_err(MH_E_DEVICE, std::string("mh_eval_values: ") + hipGetErrorString(e));
-    return MH_OK;
+    // the one-tape list, without the list entry points' 2^31-word refusal and launch count
+    return eval_values_rows(ctx, ts, nullptr, &tape, 1, as, row_first, row_count, out,
+                            "mh_eval_values", true);
 }
 
 int32_t mh_eval_values_many(mh_ctx* ctx, const mh_tapeset* ts, const uint32_t* tapes,
                             uint32_t n, const mh_assign* as, uint64_t row, uint32_t* out) {
-    return eval_values_rows(ctx, ts, nullptr, tapes, n, as, row, 1, out, "mh_eval_values_many");
+    return eval_values_rows(ctx, ts, nullptr, tapes, n, as, row, 1, out, "mh_eval_values_many",
+                            false);
 }
 
 int32_t mh_eval_values_tables(mh_ctx* ctx, const mh_tapeset* ts, const mh_tables* tables,
@@ -2067,7 +1942,7 @@ int32_t mh_eval_values_tables(mh_ctx* ctx, const mh_tapeset* ts, const mh_tables
                               uint64_t row_first, uint64_t row_count, uint32_t* out) {
     if (!tables) return set_err(MH_E_INVALID, "null table set");
     return eval_values_rows(ctx, ts, tables, tapes, n, as, row_first, row_count, out,
-                            "mh_eval_values_tables");
+                            "mh_eval_values_tables", false);
 }
 
 int32_t mh_eval_values_jobs(mh_ctx* ctx, const mh_values_job* jobs, uint32_t n_jobs) {
@@ -2118,16 +1993,6 @@ int32_t mh_eval_values_jobs(mh_ctx* ctx, const mh_values_job* jobs, uint32_t n_j
     if (slots * 8 >= (1ull << 31))
         return set_err(MH_E_INVALID, "mh_eval_values_jobs: values of 2^31 words or more in one call");
     const mh::values::Plan plan = mh::values::plan(shapes.data(), n_jobs);
-    // the spilling tapes' launch: one region, the launch's workgroup picks the wave's area
-    SpillPlan spill;
-    uint32_t spill_slots = 0;
-    for (const mh::values::Segment& sg : plan.segments)
-        if (sg.variant == mh::kSpillVariant)
-            spill_slots = std::max(spill_slots,
-                                   max_spills(jobs[sg.job].ts, plan.ids.data() + sg.first,
-                                              plan.ids.data() + sg.first + sg.n_ids));
-    for (const auto& l : plan.launches)
-        if (l.variant == mh::kSpillVariant) (void)spill.take(l.count, spill_slots);
     // the upload block: segments' KParams | block table | sorted ids
     const auto align = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_seg = 0;
@@ -2136,7 +2001,6 @@ int32_t mh_eval_values_jobs(mh_ctx* ctx, const mh_values_job* jobs, uint32_t n_j
     const size_t up_bytes = align(o_ids + plan.ids.size() * sizeof(uint32_t));
     const size_t val_bytes = (size_t)slots * 8 * sizeof(uint32_t);
     if (int32_t r = use_device(ctx)) return r;
-    if (int32_t r = spill_reserve(ctx, spill.words)) return r;
     if (int32_t r = ctx_batch_bufs(ctx, up_bytes)) return r;
     void* dval_v = nullptr;
     void* hval_v = nullptr;
@@ -2158,12 +2022,12 @@ int32_t mh_eval_values_jobs(mh_ctx* ctx, const mh_values_job* jobs, uint32_t n_j
         p.tape_ids = d_ids + sg.first;
         p.n_ids = sg.n_ids;
         p.values_out = dval + 8 * (size_t)sg.first;
-        if (sg.variant == mh::kSpillVariant) {
-            p.spill = ctx->d_spill;
-            p.spill_slots = spill_slots;
-        }
         h_seg[si] = p;
     }
+    if (int32_t r = batch_spill(ctx, plan, h_seg, [&](const mh::values::Segment& sg) {
+            return std::make_pair(jobs[sg.job].ts, plan.ids.data() + sg.first);
+        }))
+        return r;
     std::memcpy(hb + o_blk, plan.blocks.data(), plan.blocks.size() * sizeof(mh::batch::BlockEntry));
     std::memcpy(hb + o_ids, plan.ids.data(), plan.ids.size() * sizeof(uint32_t));
     hipStream_t s = ctx->stream;
@@ -2192,12 +2056,12 @@ int32_t mh_eval_values_jobs(mh_ctx* ctx, const mh_values_job* jobs, uint32_t n_j
 
 }  // extern "C"
 
-// mh_eval_values_many (tables == null: one row, tapes with lookups refused) and
-// mh_eval_values_tables: out[(i * 8 + k) * row_count + r]
+// mh_eval_values_many (tables == null: one row, tapes with lookups refused),
+// mh_eval_values_tables and mh_eval_values (`single`: its one tape): out[(i * 8 + k) * row_count + r]
 static int32_t eval_values_rows(mh_ctx* ctx, const mh_tapeset* ts, const mh_tables* tables,
                                 const uint32_t* tapes, uint32_t n, const mh_assign* as,
                                 uint64_t row, uint64_t row_count, uint32_t* out,
-                                const char* who) {
+                                const char* who, bool single) {
     if (int32_t r = check_run_args(ctx, ts, 0, 0, as, row, row_count, MH_MODE_COUNT_ALL)) return r;
     if (!tables) {
         if (int32_t r = refuse_tables(ts)) return r;
@@ -2206,78 +2070,61 @@ static int32_t eval_values_rows(mh_ctx* ctx, const mh_tapeset* ts, const mh_tabl
     }
     if (n == 0 || row_count == 0) return MH_OK;
     if (!tapes || !out) return set_err(MH_E_INVALID, "null tapes / out");
-    if ((uint64_t)n * 8 * row_count >= (1ull << 31))
+    if (!single && (uint64_t)n * 8 * row_count >= (1ull << 31))
         return set_err(MH_E_INVALID, "values of 2^31 words or more in one call");
     uint32_t top = 0;
+    std::vector<uint32_t> variants(n);
     for (uint32_t i = 0; i < n; ++i) {
         if (tapes[i] >= ts->n_tapes) return set_err(MH_E_INVALID, "tape id out of bounds");
         top = std::max(top, tapes[i]);
+        variants[i] = mh::variant_of(ts->info[tapes[i]].n_regs, ts->info[tapes[i]].features);
     }
     if (int32_t r = use_device(ctx)) return r;
-    // one launch of the production sieve kernel in values mode per register-class variant: the
-    // listed tapes of a variant are its id list, their values land at [position][8] (one row)
-    std::vector<std::pair<uint32_t, uint32_t>> by_var;  // (variant, position in `tapes`)
-    by_var.reserve(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t v = mh::variant_of(ts->info[tapes[i]].n_regs, ts->info[tapes[i]].features);
-        if (!mh::variant_fits(v, as->stride)) return refuse_capacity(as->stride);
-        by_var.push_back({v, i});
-    }
-    // by (variant, tape id, position): the kernel's chunk formation needs the ids of a launch
-    // ascending (a chunk is one contiguous range of the bucket's words, its end the last tape's);
-    // the caller's order comes back through .second below, a repeated id is evaluated again
-    std::sort(by_var.begin(), by_var.end(), [&](const auto& a, const auto& b) {
-        if (a.first != b.first) return a.first < b.first;
-        if (tapes[a.second] != tapes[b.second]) return tapes[a.second] < tapes[b.second];
-        return a.second < b.second;
-    });
-    // the spilling tapes' launch (the launches queue on one stream: one region)
-    SpillPlan spill;
-    uint32_t spill_slots = 0, n_spill = 0;
-    for (uint32_t i = 0; i < n; ++i)
-        if (by_var[i].first == mh::kSpillVariant) {
-            ++n_spill;
-            spill_slots = std::max(spill_slots, ts->spills[tapes[by_var[i].second]]);
-        }
-    if (n_spill) (void)spill.take(mh::sieve_launch_waves(row_count, n_spill, false), spill_slots);
+    // one launch of the production sieve kernel in values mode per variant: the list sorted by
+    // (variant, tape id, position) as one job of the batched planner (values_plan.h: the kernel's
+    // chunk formation needs the ids of a launch ascending; a repeated id is evaluated again; the
+    // caller's order comes back through sorted.pos), its segments as the buckets of the launch
+    // planner.  The launches queue on one stream; the spilling tapes' has one region
+    const mh::values::JobShape shape{tapes, variants.data(), n};
+    mh::values::Plan sorted = mh::values::plan(&shape, 1);
+    mh::Buckets ids;
+    for (const mh::values::Segment& sg : sorted.segments)
+        std::fill(ids.off + sg.variant + 1, ids.off + mh::kNumVariants + 1, sg.first + sg.n_ids);
+    ids.ids = std::move(sorted.ids);
+    mh::SpillPlan spill;
+    const mh::LaunchPlan plan =
+        mh::plan_launches(ids, 0, ts->n_tapes, row_count, false, false, as->stride,
+                          ts->spills.data(), spill, mh::sieve_launch_waves);
+    if (plan.misfit >= 0) return refuse_capacity(as->stride);
     if (int32_t r = spill_reserve(ctx, spill.words)) return r;
     // device block: values [n][8][rows], ids [n], first_hit / hit_count [top + 1] each (scratch:
     // the kernel's count-mode bookkeeping, indexed by tape id)
     const size_t nv = (size_t)8 * n * row_count;  // value words
     const size_t n_words = nv + n + 4 * ((size_t)top + 1) + 2 + (nv & 1);
-    std::vector<uint32_t> h(n + 4 * ((size_t)top + 1) + 2, 0u);
-    for (uint32_t i = 0; i < n; ++i) h[i] = tapes[by_var[i].second];
     // the ctx's grow-only result buffer (stream-ordered after any earlier use of it)
     void* dv = nullptr;
     MH_HIP(ctx_dbuf(ctx, n_words * sizeof(uint32_t), &dv));
     uint32_t* d = static_cast<uint32_t*>(dv);
     uint32_t* d_ids = d + nv;
     uint32_t* d_res = d_ids + n + (((nv + n) & 1) ? 1 : 0);  // 8-byte aligned
-    hipError_t e = hipMemcpyAsync(d_ids, h.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                  ctx->stream);
+    hipError_t e = hipMemcpyAsync(d_ids, ids.ids.data(), n * sizeof(uint32_t),
+                                  hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
         e = hipMemsetAsync(d_res, 0xFF, 2 * ((size_t)top + 1) * sizeof(uint32_t), ctx->stream);
     if (e == hipSuccess)
         e = hipMemsetAsync(d_res + 2 * ((size_t)top + 1), 0, 2 * ((size_t)top + 1) * sizeof(uint32_t),
                            ctx->stream);
-    uint32_t launches = 0;
-    for (uint32_t i = 0; i < n && e == hipSuccess;) {
-        uint32_t j = i;
-        while (j < n && by_var[j].first == by_var[i].first) ++j;
+    for (uint32_t k = 0; k < plan.n && e == hipSuccess; ++k) {
+        const mh::Launch& l = plan.launches[k];
         mh::KParams p = make_params(ts, 0, as, row, row_count, 0, MH_MODE_COUNT_ALL);
         p.tables = tables ? tables->d : nullptr;
-        p.tape_ids = d_ids + i;
-        p.n_ids = j - i;
+        p.tape_ids = d_ids + l.first;
+        p.n_ids = l.count;
         p.first_hit = reinterpret_cast<unsigned long long*>(d_res);
         p.hit_count = reinterpret_cast<unsigned long long*>(d_res + 2 * ((size_t)top + 1));
-        p.values_out = d + 8 * (size_t)i * row_count;
-        if (by_var[i].first == mh::kSpillVariant) {
-            p.spill = ctx->d_spill;
-            p.spill_slots = spill_slots;
-        }
-        e = mh::launch_sieve(p, by_var[i].first, ctx->stream);
-        ++launches;
-        i = j;
+        p.values_out = d + 8 * (size_t)l.first * row_count;
+        bind_spill(p, ctx, l);
+        e = mh::launch_sieve(p, l.variant, ctx->stream);
     }
     std::vector<uint32_t> vals(nv);
     if (e == hipSuccess)
@@ -2287,9 +2134,9 @@ static int32_t eval_values_rows(mh_ctx* ctx, const mh_tapeset* ts, const mh_tabl
     if (e != hipSuccess)
         return set_err(MH_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     for (uint32_t i = 0; i < n; ++i)
-        std::memcpy(out + 8 * (size_t)by_var[i].second * row_count,
+        std::memcpy(out + 8 * (size_t)sorted.pos[i] * row_count,
                     vals.data() + 8 * (size_t)i * row_count, 8 * row_count * sizeof(uint32_t));
-    ctx->eval_launches += launches;
+    if (!single) ctx->eval_launches += plan.n;  // the list entry points' counter
     return MH_OK;
 }
 
@@ -2361,18 +2208,15 @@ int32_t mh_tapes_jit(mh_tapeset* ts, uint32_t flags, uint32_t max_vgpr) {
         maxv = std::max(maxv, b.max_vgpr);
     }
     // the interpreter's buckets without the jitted tapes
-    std::vector<uint32_t> rest;
-    uint32_t boff[mh::kNumVariants + 1];
-    for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
-        boff[v] = (uint32_t)rest.size();
-        for (uint32_t i = ts->bucket_off[v]; i < ts->bucket_off[v + 1]; ++i)
-            if (!stats.jitted[ts->ids[i]]) rest.push_back(ts->ids[i]);
-    }
-    boff[mh::kNumVariants] = (uint32_t)rest.size();
+    mh::Buckets rest = mh::Buckets::build(
+        ts->n_tapes, 0,
+        [&](uint32_t t) { return mh::variant_of(ts->info[t].n_regs, ts->info[t].features); },
+        [&](uint32_t t) { return !stats.jitted[t]; });
     uint32_t* d_rest = nullptr;
-    hipError_t e = hipMalloc(&d_rest, std::max<size_t>(1, rest.size()) * sizeof(uint32_t));
-    if (e == hipSuccess && !rest.empty())
-        e = hipMemcpy(d_rest, rest.data(), rest.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    hipError_t e = hipMalloc(&d_rest, std::max<size_t>(1, rest.ids.size()) * sizeof(uint32_t));
+    if (e == hipSuccess && !rest.ids.empty())
+        e = hipMemcpy(d_rest, rest.ids.data(), rest.ids.size() * sizeof(uint32_t),
+                      hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         if (d_rest) (void)hipFree(d_rest);
         unload();
@@ -2380,9 +2224,8 @@ int32_t mh_tapes_jit(mh_tapeset* ts, uint32_t flags, uint32_t max_vgpr) {
     }
     ts->jit = std::move(mods);
     ts->jitted = stats.jitted;
-    ts->ids_rest = std::move(rest);
-    std::copy(boff, boff + mh::kNumVariants + 1, ts->bucket_off_rest);
-    ts->d_ids_rest = d_rest;
+    ts->rest = std::move(rest);
+    ts->d_rest = d_rest;
     ts->has_jit = true;
     ts->code_id = code_id;
     mh_jit_info& ji = ts->jinfo;
@@ -2627,20 +2470,6 @@ struct mh_repair {
     std::vector<mh_elite> elites;
 };
 
-static int32_t repair_span(mh_ctx* ctx, bool end) {  // mh_ctx_kernel_time counts repair launches too
-    if (!ctx->timing) return MH_OK;
-    if (!end) {
-        std::pair<hipEvent_t, hipEvent_t> sp{nullptr, nullptr};
-        MH_HIP(hipEventCreate(&sp.first));
-        MH_HIP(hipEventCreate(&sp.second));
-        ctx->spans.push_back(sp);
-        MH_HIP(hipEventRecord(sp.first, ctx->stream));
-    } else {
-        MH_HIP(hipEventRecord(ctx->spans.back().second, ctx->stream));
-    }
-    return MH_OK;
-}
-
 int32_t mh_repair_create(mh_ctx* ctx, uint32_t max_conjuncts, uint32_t max_rows,
                          uint32_t max_elites, mh_repair** out) {
     if (!ctx || !out) return set_err(MH_E_INVALID, "null argument");
@@ -2705,37 +2534,25 @@ int32_t mh_repair_score(mh_repair* r, const mh_tapeset* ts, uint32_t tape_first,
     p.masks = r->d_masks;
     p.mask_base = tape_first;
     p.mask_stride = stride;
-    // the conjunct tapes of each kernel-variant bucket inside the range, refused before a launch
-    const uint32_t *lo[mh::kNumVariants], *hi[mh::kNumVariants];
-    for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
-        const uint32_t* b = ts->ids.data() + ts->bucket_off[v];
-        const uint32_t* e = ts->ids.data() + ts->bucket_off[v + 1];
-        lo[v] = std::lower_bound(b, e, tape_first);
-        hi[v] = std::lower_bound(lo[v], e, tape_first + tape_count);
-        if (hi[v] != lo[v] && !mh::variant_fits(v, p.capacity)) return refuse_capacity(p.capacity);
-    }
-    SpillPlan spill;
-    const uint32_t *slo = lo[mh::kSpillVariant], *shi = hi[mh::kSpillVariant];
-    const uint32_t spill_slots = max_spills(ts, slo, shi);
-    if (shi != slo)
-        (void)spill.take(mh::sieve_launch_waves(row_count, (uint32_t)(shi - slo), true), spill_slots);
+    // a masks-mode launch per kernel-variant bucket of the conjunct tapes, refused before a launch
+    mh::SpillPlan spill;
+    const mh::LaunchPlan plan =
+        mh::plan_launches(ts->all, tape_first, tape_count, row_count, false, true, p.capacity,
+                          ts->spills.data(), spill, mh::sieve_launch_waves);
+    if (plan.misfit >= 0) return refuse_capacity(p.capacity);
     if (int32_t rc = spill_reserve(ctx, spill.words)) return rc;
     r->scored = r->selected = false;
-    if (int32_t rc = repair_span(ctx, false)) return rc;
-    for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
-        if (hi[v] == lo[v]) continue;
+    MH_HIP(span_begin(ctx));
+    for (uint32_t k = 0; k < plan.n; ++k) {
         mh::KParams q = p;
-        q.tape_ids = ts->d_ids + (lo[v] - ts->ids.data());
-        q.n_ids = (uint32_t)(hi[v] - lo[v]);
-        if (v == mh::kSpillVariant) {
-            q.spill = ctx->d_spill;
-            q.spill_slots = spill_slots;
-        }
-        MH_HIP(mh::launch_sieve(q, v, ctx->stream));
+        q.tape_ids = ts->d_all + plan.launches[k].first;
+        q.n_ids = plan.launches[k].count;
+        bind_spill(q, ctx, plan.launches[k]);
+        MH_HIP(mh::launch_sieve(q, plan.launches[k].variant, ctx->stream));
     }
     MH_HIP(mh::launch_fail_count(r->d_masks, stride, tape_count, (uint32_t)row_count, r->d_fail,
                                  ctx->stream));
-    if (int32_t rc = repair_span(ctx, true)) return rc;
+    MH_HIP(span_end(ctx));
     r->n_conj = tape_count;
     r->row_first = (uint32_t)row_first;
     r->row_count = (uint32_t)row_count;
@@ -2759,10 +2576,10 @@ int32_t mh_repair_select(mh_repair* r, uint32_t k, uint64_t seed, mh_elite* out,
     if (int32_t rc = use_device(ctx)) return rc;
     const uint32_t n = std::min(k, r->row_count);
     r->selected = false;
-    if (int32_t rc = repair_span(ctx, false)) return rc;
+    MH_HIP(span_begin(ctx));
     MH_HIP(mh::launch_select(r->d_masks, r->stride, r->n_conj, r->d_fail, r->row_first,
                              r->row_count, n, seed, r->d_elites, ctx->stream));
-    if (int32_t rc = repair_span(ctx, true)) return rc;
+    MH_HIP(span_end(ctx));
     r->elites.assign(n, mh_elite{});
     MH_HIP(hipMemcpyAsync(r->elites.data(), r->d_elites, n * sizeof(mh_elite),
                           hipMemcpyDeviceToHost, ctx->stream));
@@ -2825,11 +2642,11 @@ int32_t mh_repair_mutate(mh_repair* r, const mh_assign* src, mh_assign* dst, con
     }
     MH_HIP(hipMemcpyAsync(r->d_plan, r->h_plan.data(), words * sizeof(uint32_t),
                           hipMemcpyHostToDevice, ctx->stream));
-    if (int32_t rc = repair_span(ctx, false)) return rc;
+    MH_HIP(span_begin(ctx));
     MH_HIP(mh::launch_mutate(src->d, src->stride, dst->d, dst->stride, dst->n_vars, r->d_elites,
                              n_el, per, flags, seed, global_base, k, r->d_plan + o_tag,
                              r->d_plan + o_off, r->d_plan + o_cols, ctx->stream));
-    if (int32_t rc = repair_span(ctx, true)) return rc;
+    MH_HIP(span_end(ctx));
     MH_HIP(hipStreamSynchronize(ctx->stream));  // h_plan is pageable: done with it on return
     return MH_OK;
 }

@@ -1,4 +1,5 @@
-// Launch interface between the C-ABI layer (capi.cpp) and the kernels (sieve_kernels.hip).
+// Launch interface between the C-ABI layer (capi.cpp) and the kernels (sieve_kernels.hip).  The
+// kernel variants' numbering is variants.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -6,6 +7,7 @@
 #include "../../include/mythril_hip.h"
 #include "batch_plan.h"
 #include "dev_isa.h"
+#include "variants.h"
 
 namespace mh {
 
@@ -43,43 +45,9 @@ struct KParams {
     uint32_t spill_slots;
     uint32_t pad3;
 };
-// words of spill memory a launch of `waves` waves needs
-inline uint64_t spill_words(uint64_t waves, uint32_t spill_slots) {
-    return waves * spill_slots * MH_SPILL_SLOT_WORDS;
-}
-
-// Kernel variants: register-file size class (NR 7 / 9 / 15) x feature set (asm only / + C++
-// complex ops / + keccak / + keccak and the EVM helpers).  Keccak tapes get a kernel without the
-// EVM helpers' register footprint.
-inline uint32_t nr_class(uint32_t n_regs) {
-    return n_regs <= MH_NR_SMALL ? 0u : n_regs <= MH_NR_MID ? 1u : 2u;
-}
-// Tapes with a table lookup (F_TABLE: the certifier's, never a query round's) get a feature class
-// of their own with every handler, one kernel per register class, numbered after the twelve.
-constexpr uint32_t kFirstTableVariant = 12;
-// Tapes that spill (F_SPILL: more live values than MH_NR_MAX registers, compile.cpp) run in one
-// kernel of their own, NR = 15 with every handler, the table lookup included, and the spill ops:
-// no other variant carries a case, a branch or a register for them.
-constexpr uint32_t kSpillVariant = 15;
-inline uint32_t variant_of(uint32_t n_regs, uint32_t features) {
-    if (features & F_SPILL) return kSpillVariant;
-    if (features & F_TABLE) return kFirstTableVariant + nr_class(n_regs);  // 12..14
-    const uint32_t fc = (features & F_EVM) ? 3u : (features & F_KECCAK) ? 2u
-                        : (features & F_CPLX) ? 1u : 0u;
-    return nr_class(n_regs) * 4 + fc;  // 0..11
-}
-constexpr uint32_t kNumVariants = 16;
-// The complex-op variants (feature class != 0) load columns inside the asm core (run_lv) with a
-// 32-bit byte stride per limb plane: their buffers hold fewer than 2^30 rows per column.  The
-// asm-only variants index columns with 64-bit arithmetic and take any capacity.
-constexpr uint64_t kLoadvarMaxCapacity = 1ull << 30;
-inline bool variant_fits(uint32_t variant, uint64_t capacity) {
-    return (variant < kFirstTableVariant && (variant & 3u) == 0) || capacity < kLoadvarMaxCapacity;
-}
-
 hipError_t launch_sieve(const KParams& p, uint32_t variant, hipStream_t stream);
 // waves launch_sieve starts for a run of row_count rows over n_ids tapes (what the spill variant's
-// region is sized by: spill_words(sieve_launch_waves(..), spill_slots))
+// region is sized by: launch_plan.h plan_launches takes spill_words(waves, spill_slots) per launch)
 uint64_t sieve_launch_waves(uint64_t row_count, uint32_t n_ids, bool masks);
 hipError_t launch_generate(uint32_t* assign, uint64_t stride, uint64_t rows, uint32_t n_vars,
                            uint64_t seed, uint64_t base, hipStream_t stream);

@@ -10,7 +10,9 @@
 // the unit that gets a KParams on the device.  Slot s holds the value of the job's list position
 // pos[s]; the kernel writes it at value word 8 s of the submission's value block.  One launch per
 // variant present, table variants (12..14) included, so a tape runs the kernel the single calls
-// (mh_eval_values_many / mh_eval_values_tables) run it with.
+// (mh_eval_values / mh_eval_values_many / mh_eval_values_tables) run it with: those sort their one
+// list with this planner too (capi.cpp eval_values_rows: a single job, a direct launch per segment
+// planned by launch_plan.h).
 #pragma once
 #include <stdint.h>
 
@@ -18,13 +20,14 @@
 #include <vector>
 
 #include "batch_plan.h"
+#include "variants.h"
 
 namespace mh {
 namespace values {
 
-constexpr uint32_t kVariants = 15;    // without spill code: 0..11 table-free, 12..14 table
-constexpr uint32_t kSpillVariant = 15;  // kernels.h kSpillVariant: the tapes that spill, after them
-constexpr uint32_t kAllVariants = 16;   // kernels.h kNumVariants
+// (variants.h) without spill code: 0..11 table-free, 12..14 table; the spill variant after them
+constexpr uint32_t kVariants = kSpillVariant;
+constexpr uint32_t kAllVariants = kNumVariants;
 constexpr uint32_t kJobsMax = 256;    // MH_VALUES_JOBS_MAX
 constexpr uint32_t kMinBlocks = 256;  // launch_block's target: a workgroup per CU
 

@@ -87,6 +87,36 @@ def test_mixed_set_splits_into_variants(gpu_ctx, n_cols):
     check_counts(gpu_ctx, sc.mixed_set(n_cols, plain=True), 209, 37, _want(n_cols, plain=True))
 
 
+def test_sub_range_cuts_the_spill_bucket(gpu_ctx):
+    """A run over tapes [tape_first, tape_first + tape_count) of the mixed set, both chosen from
+    the set's spills() so that spilled and fitting tapes lie inside and outside the range: the
+    spill variant's launch starts inside its bucket (a spill region for a part of the bucket's
+    tapes), the results indexed from tape_first."""
+    ts = sc.mixed_set(6, plain=True)
+    rows, row_first = 209, 37
+    ct = gpu_ctx.compile(ts)
+    a = gpu_ctx.assignments(ts.n_vars, row_first + rows)
+    try:
+        s = [int(x) for x in ct.spills()]
+        fit = [t for t in range(len(s)) if s[t] == 0]
+        first, end = fit[0] + 1, fit[-1] + 2
+        inside, outside = s[first:end], s[:first] + s[end:]
+        assert 0 in inside and any(inside) and 0 in outside and any(outside), s
+        a.generate(SEED, BASE)
+        cnt, hit = ctape.count(ts, SEED, BASE + row_first, rows,
+                               threads=min(16, os.cpu_count() or 1))
+        for mode in (native.MODE_COUNT_ALL, native.MODE_FIRST_HIT):
+            fh, hc = native.run(gpu_ctx, ct, a, tape_first=first, tape_count=end - first,
+                                row_first=row_first, row_count=rows, index_base=BASE, mode=mode)
+            assert np.array_equal(fh, hit[first:end]), (mode, fh, hit[first:end])
+            if mode == native.MODE_COUNT_ALL:
+                assert np.array_equal(hc, cnt[first:end]), (hc, cnt[first:end])
+        assert np.count_nonzero(cnt[first:end]) >= (end - first) // 2, "most tapes count some hits"
+    finally:
+        a.close()
+        ct.close()
+
+
 def test_wide_fuzz_tapes(gpu_ctx):
     """150 fuzz tapes over six columns in one set (most spill), 128 rows: the sample on which
     spilled tapes over loaded columns once counted wrong in some lanes."""
@@ -127,6 +157,28 @@ def test_values_mode(gpu_ctx):
                                                  (ct, None, [2], a, 4)])
         assert [word(jobs[0][i]) for i in range(3)] == [want[t][2] for t in range(3)]
         assert word(jobs[1][0]) == want[2][4]
+    finally:
+        a.close()
+        ct.close()
+
+
+def test_values_mode_two_waves(gpu_ctx):
+    """mh_eval_values of the spilled fan tape above over 65 rows: two waves, the smallest run
+    with more than one wave's spill area; every row's value against the Python oracle."""
+    ts = TapeSet(["x0", "x1"])
+    b = ts.builder()
+    ts.add(b.finish(sc.fan_nodes(b, 24, 2)[0]))
+    rows = sc.edge_rows(2, 65, 7)
+    ct = gpu_ctx.compile(ts)
+    a = gpu_ctx.assignments(2, len(rows))
+    try:
+        assert ct.spills()[0] > 0
+        a.upload(sc.soa(rows, 2))
+        got = native.eval_values(gpu_ctx, ct, 0, a, 0, len(rows))
+        assert got.shape == (8, 65)
+        for r, row in enumerate(rows):
+            want = int(E.evaluate(ts.tapes[0].nodes, ts.pool.values, row))
+            assert sum(int(got[k, r]) << (32 * k) for k in range(8)) == want, r
     finally:
         a.close()
         ct.close()

@@ -157,6 +157,12 @@ int32_t mh_tapes_info(const mh_tapeset* ts, mh_tape_info* info /* [n_tapes] */, 
  * the ctx owns, and runs in a kernel of its own.  A run whose spill areas would exceed 256 MiB is
  * MH_E_UNSUPPORTED, refused before anything is queued.                                           */
 int32_t mh_tapes_spills(const mh_tapeset* ts, uint32_t* out /* [n_tapes] */, uint32_t n_tapes);
+/* Read-only: which tapes mh_tapes_compile cut into conjunct parts (MH_SPLIT_INSNS; a run of at
+ * most MH_SPLIT_ROWS rows walks the parts and ANDs their masks).  *n_split = the split tapes,
+ * *n_parts = the parts of all of them, tape_parts[t] = the parts of tape t (0: it runs whole).
+ * Each output may be NULL.                                                                      */
+int32_t mh_tapes_split_info(const mh_tapeset* ts, uint32_t* n_split, uint32_t* n_parts,
+                            uint32_t* tape_parts /* [n_tapes] or NULL */, uint32_t n_tapes);
 
 /* ---- assignments ----------------------------------------------------------------------------- */
 /* Layout in HBM: column v, limb k (0 = least significant) of assignment i is word

@@ -1072,6 +1072,20 @@ int32_t mh_tapes_spills(const mh_tapeset* ts, uint32_t* out, uint32_t n_tapes) {
     return MH_OK;
 }
 
+int32_t mh_tapes_split_info(const mh_tapeset* ts, uint32_t* n_split, uint32_t* n_parts,
+                            uint32_t* tape_parts, uint32_t n_tapes) {
+    if (!ts) return set_err(MH_E_INVALID, "null argument");
+    if (n_tapes > ts->n_tapes) return set_err(MH_E_INVALID, "n_tapes exceeds the tape set");
+    if (n_split) *n_split = (uint32_t)(ts->split_tab.size() / 3);
+    if (n_parts) *n_parts = ts->n_parts;
+    if (tape_parts) {
+        std::fill(tape_parts, tape_parts + n_tapes, 0u);
+        for (size_t i = 0; i < ts->split_tab.size(); i += 3)
+            if (ts->split_tab[i] < n_tapes) tape_parts[ts->split_tab[i]] = ts->split_tab[i + 2];
+    }
+    return MH_OK;
+}
+
 int32_t mh_tapes_info(const mh_tapeset* ts, mh_tape_info* info, uint32_t n_tapes) {
     if (!ts || !info) return set_err(MH_E_INVALID, "null argument");
     if (n_tapes > ts->n_tapes) return set_err(MH_E_INVALID, "n_tapes exceeds the tape set");

@@ -58,6 +58,7 @@ SIGNATURES = {
     "mh_tapes_destroy": (C.c_int32, [_vp]),
     "mh_tapes_info": (C.c_int32, [_vp, _vp, C.c_uint32]),
     "mh_tapes_spills": (C.c_int32, [_vp, _vp, C.c_uint32]),
+    "mh_tapes_split_info": (C.c_int32, [_vp, _u32p, _u32p, _vp, C.c_uint32]),
     "mh_assign_create": (C.c_int32, [_vp, C.c_uint32, C.c_uint64, C.POINTER(_vp)]),
     "mh_assign_destroy": (C.c_int32, [_vp]),
     "mh_assign_upload": (C.c_int32, [_vp, _u32p, C.c_uint64, C.c_uint64]),
@@ -1051,6 +1052,15 @@ class CompiledTapes:
         out = np.zeros(max(self.n_tapes, 1), dtype=np.uint32)
         _check(self.ctx.lib.mh_tapes_spills(self.h, _ptr(out), self.n_tapes))
         return out[: self.n_tapes]
+
+    def split_info(self) -> Tuple[int, int, np.ndarray]:
+        """(split tapes, their parts in all, parts per tape: 0 for a tape that runs whole)
+        (mh_tapes_split_info): what MH_SPLIT_INSNS made of the set at compile time."""
+        n_split, n_parts = C.c_uint32(), C.c_uint32()
+        out = np.zeros(max(self.n_tapes, 1), dtype=np.uint32)
+        _check(self.ctx.lib.mh_tapes_split_info(self.h, C.byref(n_split), C.byref(n_parts),
+                                                out.ctypes.data, self.n_tapes))
+        return n_split.value, n_parts.value, out[: self.n_tapes]
 
     def close(self) -> None:
         if self.h:

@@ -759,6 +759,11 @@ def test_conjunct_parallel_split_runs(gpu_ctx, rows):
         else:
             os.environ["MH_SPLIT_INSNS"] = old
     n = len(ts.tapes)
+    # not vacuous: MH_SPLIT_INSNS=8 did cut tapes into parts, MH_SPLIT_INSNS=0 none
+    assert whole.split_info()[:2] == (0, 0) and not whole.split_info()[2].any()
+    n_split, n_parts, parts = cut.split_info()
+    assert n_split >= 1 and n_parts >= 2 * n_split, (n_split, n_parts)
+    assert n_split == np.count_nonzero(parts) and n_parts == int(parts.sum()), parts
     for mode in (native.MODE_FIRST_HIT, native.MODE_COUNT_ALL):
         for first, count in ((0, n), (3, n - 5), (n - 1, 1)):
             want = native.run(gpu_ctx, whole, a, tape_first=first, tape_count=count, mode=mode,

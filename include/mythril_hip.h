@@ -625,6 +625,66 @@ int32_t mh_repair_mutate(mh_repair* r, const mh_assign* src, mh_assign* dst, con
                          const uint32_t* conj_cols, uint32_t n_conjuncts, uint32_t per,
                          uint32_t flags, uint64_t seed, uint64_t global_base);
 
+/* ---- hit listing (no reference counterpart; DESIGN.md §6 "Spare witnesses") --------------------
+ * mh_run hands back a tape's smallest satisfying row and drops the others.  mh_run_hits lists the
+ * k smallest.  Opt-in (Sieve(spares=...)); nothing else in the library calls these three.
+ *
+ * mh_run_hits: tapes [tape_first, tape_first + tape_count) over rows [row_first, row_first +
+ * row_count) of `as`, every (tape, row) Bool determined as in MH_MODE_COUNT_ALL.  Per tape t
+ * (indexed by tape - tape_first): hits[t][0..n_hits[t]) = the min(k, hit_count[t]) smallest
+ * satisfying rows as GLOBAL indices (index_base + row), ascending; hits[t][j] = MH_NO_HIT for
+ * j >= n_hits[t]; hit_count[t] = all satisfying rows of the range; rows_out[t][j] = columns
+ * 0..n_cols-1 of the row hits[t][j] names, all zero for a slot without a hit.  With k == 1, hits,
+ * hit_count and rows_out equal what mh_run_rows(..., MH_MODE_COUNT_ALL, ...) writes, bit for bit.
+ * The run walks whole tapes with the interpreter (the native code of mh_tapes_jit and split-tape
+ * parts are not used), each wave writing its 64-row Bool mask per tape: one launch per
+ * kernel-variant bucket, spilled tapes in a launch of their own; then one select launch (a
+ * workgroup per tape: a prefix sum over the masks' popcounts, so the list does not depend on
+ * scheduling), one row gather, one copy back and one sync.  Blocks until done.
+ *
+ * mh_assign_scatter: values[r][c][0..7] into column cols[c] of buffer row first + r, for r <
+ * n_rows and c < n_cols; every other column of those rows keeps its content.  Values are stored as
+ * given (no masking to a column width).  cols must be strictly ascending and inside the buffer's
+ * columns, first + n_rows within its capacity.  n_rows == 0 or n_cols == 0 is MH_OK and launches
+ * nothing.  Queues on the ctx stream and returns, as mh_assign_generate_guided does (the arrays
+ * are copied before it returns).
+ *
+ * mh_query_round_hits: one guided round with a listing, in one call: mh_assign_generate_guided of
+ * rows [0, count); then, when `spares` is given, mh_assign_scatter of its rows into rows [0,
+ * spares->n_rows) -- rows the caller wants tried first, such as models of an ancestor query; then
+ * mh_run_hits over [0, count) with index_base = global_base.  One host sync.  With spares == NULL
+ * and k == 1 the outputs and the buffer's contents afterwards equal
+ * mh_query_round(..., MH_MODE_COUNT_ALL, ...)'s.
+ *
+ * Refusals, all before anything is queued or any device call is made; the message names the
+ * argument.  MH_E_INVALID: a null or foreign handle, null hits / n_hits, k outside
+ * 1..MH_HITS_MAX, row_count (count) outside 1..MH_HITS_MAX_ROWS or beyond the buffer, n_cols
+ * beyond the buffer's columns, rows_out NULL with n_cols > 0, spares->n_rows > count, cols not
+ * strictly ascending or outside the buffer.  MH_E_UNSUPPORTED: a tape set holding a lookup, a
+ * kernel variant the buffer's capacity does not fit, spill areas beyond the cap.  With
+ * mh_ctx_enable_timing a submission is one span.                                                 */
+#define MH_HITS_MAX 64          /* k */
+#define MH_HITS_MAX_ROWS 65536  /* rows of one listing run (the sieve's largest round) */
+int32_t mh_run_hits(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first, uint32_t tape_count,
+                    const mh_assign* as, uint64_t row_first, uint64_t row_count,
+                    uint64_t index_base, uint32_t k, uint64_t* hits /* [tape_count][k] */,
+                    uint32_t* n_hits /* [tape_count] */,
+                    uint64_t* hit_count /* [tape_count] or NULL */, uint32_t n_cols,
+                    uint32_t* rows_out /* [tape_count][k][n_cols][8]; NULL iff n_cols == 0 */);
+int32_t mh_assign_scatter(mh_assign* as, uint64_t first, uint32_t n_rows, const uint32_t* cols,
+                          uint32_t n_cols, const uint32_t* values /* [n_rows][n_cols][8] */);
+typedef struct mh_spares {
+    uint32_t n_rows, n_cols;
+    const uint32_t* cols;    /* [n_cols] strictly ascending                                      */
+    const uint32_t* values;  /* [n_rows][n_cols][8]                                              */
+} mh_spares;
+int32_t mh_query_round_hits(mh_ctx* ctx, const mh_tapeset* ts, mh_assign* as, const mh_guide* guide,
+                            uint64_t seed, uint64_t global_base, uint64_t count,
+                            uint32_t tape_first, uint32_t tape_count,
+                            const mh_spares* spares /* NULL: none */, uint32_t k, uint64_t* hits,
+                            uint32_t* n_hits, uint64_t* hit_count, uint32_t n_cols,
+                            uint32_t* rows_out);
+
 /* ---- decision by enumeration (no reference counterpart; DESIGN.md §6 "Decision by enumeration") --
  * A group whose columns all have small provable domains is decided exactly: the device writes the
  * cross product of the domains in order, the interpreter runs the group's tape over it, and the

@@ -102,6 +102,10 @@ struct mh_ctx {
     // launches are ordered after them (the side streams fork from and join into `stream`)
     uint32_t* d_spill = nullptr;
     size_t spill_bytes = 0;
+    // the wave masks of a hit-listing run (mh_run_hits; grow-only).  Not d_masks: a split-tape run
+    // writes that one.
+    unsigned long long* d_hit_masks = nullptr;
+    size_t hit_masks_bytes = 0;
 };
 
 // One compile at a time, handed to a worker thread that waits on a condition variable (a thread
@@ -308,6 +312,13 @@ struct mh_assign {
     size_t pinned_words = 0;
     hipEvent_t staged = nullptr;   // recorded after the staging copy; reuse waits on it
     bool staged_pending = false;
+    // mh_assign_scatter: cols | values, pinned staging and device copy (grow-only), with an event
+    // of their own so that a scatter queued behind a generator does not wait for the guide's copy
+    uint32_t* h_scatter = nullptr;
+    uint32_t* d_scatter = nullptr;
+    size_t h_scatter_bytes = 0, d_scatter_bytes = 0;
+    hipEvent_t scattered = nullptr;
+    bool scatter_pending = false;
 };
 
 namespace {
@@ -676,6 +687,7 @@ void ctx_free(mh_ctx* ctx) {
     if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
     if (ctx->d_masks) (void)hipFree(ctx->d_masks);
     if (ctx->d_spill) (void)hipFree(ctx->d_spill);
+    if (ctx->d_hit_masks) (void)hipFree(ctx->d_hit_masks);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->d_buf) (void)hipFree(ctx->d_buf);
     if (ctx->h_buf) (void)hipHostFree(ctx->h_buf);
@@ -1134,6 +1146,10 @@ int32_t mh_assign_destroy(mh_assign* as) {
     if (as->staged_pending) (void)hipEventSynchronize(as->staged);
     if (as->staged) (void)hipEventDestroy(as->staged);
     if (as->h_pinned) (void)hipHostFree(as->h_pinned);
+    if (as->scatter_pending) (void)hipEventSynchronize(as->scattered);
+    if (as->scattered) (void)hipEventDestroy(as->scattered);
+    if (as->h_scatter) (void)hipHostFree(as->h_scatter);
+    if (as->d_scatter) (void)hipFree(as->d_scatter);
     if (as->d) (void)hipFree(as->d);
     if (as->d_guide) (void)hipFree(as->d_guide);
     mh_ctx* ctx = as->ctx;
@@ -2663,6 +2679,204 @@ int32_t mh_repair_mutate(mh_repair* r, const mh_assign* src, mh_assign* dst, con
     MH_HIP(span_end(ctx));
     MH_HIP(hipStreamSynchronize(ctx->stream));  // h_plan is pageable: done with it on return
     return MH_OK;
+}
+
+// ---- hit listing and the scatter (include/mythril_hip.h; kernels in hits.hip) -------------------
+namespace {
+
+// mh_run_hits' arguments, checked without a device call.  k and the row count come before any
+// handle is read.
+int32_t check_hits_args(const mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first,
+                        uint32_t tape_count, const mh_assign* as, uint64_t row_first,
+                        uint64_t row_count, uint32_t k, const uint64_t* hits, const uint32_t* n_hits,
+                        uint32_t n_cols, const uint32_t* rows_out, const char* who) {
+    const std::string w = std::string(who) + ": ";
+    if (!ctx || !ts || !as) return set_err(MH_E_INVALID, w + "null handle (ctx, ts or as)");
+    if (k < 1 || k > MH_HITS_MAX)
+        return set_err(MH_E_INVALID, w + "k = " + std::to_string(k) + " outside 1..MH_HITS_MAX");
+    if (row_count < 1 || row_count > MH_HITS_MAX_ROWS)
+        return set_err(MH_E_INVALID, w + "row_count = " + std::to_string(row_count) +
+                                         " outside 1..MH_HITS_MAX_ROWS");
+    if (!hits || !n_hits) return set_err(MH_E_INVALID, w + "null hits or n_hits");
+    if (int32_t r = check_run_args(ctx, ts, tape_first, tape_count, as, row_first, row_count,
+                                   MH_MODE_COUNT_ALL))
+        return r;
+    if (n_cols > as->n_vars)
+        return set_err(MH_E_INVALID, w + "n_cols beyond the buffer's columns");
+    if (n_cols && !rows_out) return set_err(MH_E_INVALID, w + "rows_out null with n_cols > 0");
+    return refuse_tables(ts);
+}
+
+// mh_assign_scatter's arguments, checked without a device call.  The order of `cols` comes before
+// the handle is read.
+int32_t check_scatter_args(const mh_assign* as, uint64_t first, uint32_t n_rows,
+                           const uint32_t* cols, uint32_t n_cols, const uint32_t* values,
+                           const char* who) {
+    const std::string w = std::string(who) + ": ";
+    if (!as) return set_err(MH_E_INVALID, w + "null handle (as)");
+    if (n_rows && n_cols && (!cols || !values)) return set_err(MH_E_INVALID, w + "null cols or values");
+    if (n_rows && cols)
+        for (uint32_t c = 1; c < n_cols; ++c)
+            if (cols[c] <= cols[c - 1])
+                return set_err(MH_E_INVALID, w + "cols not strictly ascending");
+    if (n_rows && n_cols && cols[n_cols - 1] >= as->n_vars)
+        return set_err(MH_E_INVALID, w + "cols beyond the buffer's columns");
+    if (first > as->capacity || n_rows > as->capacity - first)
+        return set_err(MH_E_INVALID, w + "rows first + n_rows beyond the buffer's capacity");
+    return MH_OK;
+}
+
+// A checked scatter queued on the ctx stream: cols | values through the buffer's pinned staging.
+int32_t scatter_queue(mh_assign* as, uint64_t first, uint32_t n_rows, const uint32_t* cols,
+                      uint32_t n_cols, const uint32_t* values) {
+    if (n_rows == 0 || n_cols == 0) return MH_OK;
+    if (int32_t r = use_device(as->ctx)) return r;
+    const size_t n_val = (size_t)n_rows * n_cols * 8;
+    const size_t bytes = (n_cols + n_val) * sizeof(uint32_t);
+    if (as->scatter_pending) {  // the last scatter's copy still reads the staging area
+        MH_HIP(hipEventSynchronize(as->scattered));
+        as->scatter_pending = false;
+    }
+    if (bytes > as->d_scatter_bytes) {
+        // a queued scatter kernel may still read the old device block
+        MH_HIP(hipStreamSynchronize(as->ctx->stream));
+        MH_HIP(grow_buf(&as->d_scatter, &as->d_scatter_bytes, bytes, 1 << 14, false));
+    }
+    MH_HIP(grow_buf(&as->h_scatter, &as->h_scatter_bytes, bytes, 1 << 14, true));
+    if (!as->scattered) MH_HIP(hipEventCreateWithFlags(&as->scattered, hipEventDisableTiming));
+    std::memcpy(as->h_scatter, cols, n_cols * sizeof(uint32_t));
+    std::memcpy(as->h_scatter + n_cols, values, n_val * sizeof(uint32_t));
+    MH_HIP(hipMemcpyAsync(as->d_scatter, as->h_scatter, bytes, hipMemcpyHostToDevice,
+                          as->ctx->stream));
+    MH_HIP(hipEventRecord(as->scattered, as->ctx->stream));
+    as->scatter_pending = true;
+    MH_HIP(mh::launch_scatter(as->d, as->stride, first, n_rows, as->d_scatter, n_cols,
+                              as->d_scatter + n_cols, as->ctx->stream));
+    return MH_OK;
+}
+
+// A hit-listing run, planned: everything that can refuse it or has to allocate happens in
+// hits_plan, before anything of the call is queued; hits_submit queues and waits.
+struct HitsPlan {
+    mh::LaunchPlan plan;
+    uint64_t stride = 0;  // mask words per tape
+    size_t n = 0;         // max(tape_count, 1)
+    size_t o_count = 0, o_n = 0, o_rows = 0, bytes = 0;  // the result block: hits | counts | n | rows
+    void *d = nullptr, *h = nullptr;
+};
+
+int32_t hits_plan(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first, uint32_t tape_count,
+                  const mh_assign* as, uint64_t row_count, uint32_t k, uint32_t n_cols,
+                  HitsPlan* hp) {
+    hp->stride = mh::sieve_mask_stride(row_count);
+    mh::SpillPlan spill;
+    hp->plan = mh::plan_launches(ts->all, tape_first, tape_count, row_count, false, true,
+                                 as->stride, ts->spills.data(), spill, mh::sieve_launch_waves);
+    if (hp->plan.misfit >= 0) return refuse_capacity(as->stride);
+    if (int32_t r = use_device(ctx)) return r;
+    if (int32_t r = spill_reserve(ctx, spill.words)) return r;
+    hp->n = std::max<uint32_t>(tape_count, 1);
+    hp->o_count = hp->n * k * sizeof(uint64_t);
+    hp->o_n = hp->o_count + hp->n * sizeof(uint64_t);
+    hp->o_rows = hp->o_n + (hp->n * sizeof(uint32_t) + 7) / 8 * 8;
+    hp->bytes = hp->o_rows + (size_t)tape_count * k * n_cols * 8 * sizeof(uint32_t);
+    // grow-only buffers: a call ends with a stream sync, so nothing queued uses the old blocks
+    MH_HIP(grow_buf(&ctx->d_hit_masks, &ctx->hit_masks_bytes,
+                    (size_t)hp->n * hp->stride * sizeof(unsigned long long), 1 << 16, false));
+    MH_HIP(ctx_dbuf(ctx, hp->bytes, &hp->d));
+    MH_HIP(ctx_hbuf(ctx, hp->bytes, &hp->h));
+    return MH_OK;
+}
+
+int32_t hits_submit(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first, uint32_t tape_count,
+                    const mh_assign* as, uint64_t row_first, uint64_t row_count,
+                    uint64_t index_base, uint32_t k, const HitsPlan& hp, uint64_t* hits,
+                    uint32_t* n_hits, uint64_t* hit_count, uint32_t n_cols, uint32_t* rows_out) {
+    if (tape_count == 0) return MH_OK;
+    char* d = static_cast<char*>(hp.d);
+    const char* h = static_cast<const char*>(hp.h);
+    uint64_t* d_hits = reinterpret_cast<uint64_t*>(d);
+    mh::KParams p = make_params(ts, tape_first, as, row_first, row_count, index_base,
+                                MH_MODE_COUNT_ALL);
+    p.masks = ctx->d_hit_masks;
+    p.mask_base = tape_first;
+    p.mask_stride = hp.stride;
+    MH_HIP(span_begin(ctx));
+    for (uint32_t i = 0; i < hp.plan.n; ++i) {
+        mh::KParams q = p;
+        q.tape_ids = ts->d_all + hp.plan.launches[i].first;
+        q.n_ids = hp.plan.launches[i].count;
+        bind_spill(q, ctx, hp.plan.launches[i]);
+        MH_HIP(mh::launch_sieve(q, hp.plan.launches[i].variant, ctx->stream));
+    }
+    MH_HIP(mh::launch_hits_select(ctx->d_hit_masks, hp.stride, tape_count, (uint32_t)row_count,
+                                  index_base + row_first, k, d_hits,
+                                  reinterpret_cast<uint32_t*>(d + hp.o_n),
+                                  reinterpret_cast<uint64_t*>(d + hp.o_count), ctx->stream));
+    MH_HIP(mh::launch_hits_rows(as->d, as->stride, d_hits, tape_count, k, index_base, n_cols,
+                                reinterpret_cast<uint32_t*>(d + hp.o_rows), ctx->stream));
+    MH_HIP(span_end(ctx));
+    // lists, counts and rows in one copy into pinned memory
+    MH_HIP(hipMemcpyAsync(hp.h, hp.d, hp.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(hipStreamSynchronize(ctx->stream));
+    std::memcpy(hits, h, (size_t)tape_count * k * sizeof(uint64_t));
+    if (hit_count) std::memcpy(hit_count, h + hp.o_count, tape_count * sizeof(uint64_t));
+    std::memcpy(n_hits, h + hp.o_n, tape_count * sizeof(uint32_t));
+    if (n_cols) std::memcpy(rows_out, h + hp.o_rows, hp.bytes - hp.o_rows);
+    return MH_OK;
+}
+
+}  // namespace
+
+int32_t mh_run_hits(mh_ctx* ctx, const mh_tapeset* ts, uint32_t tape_first, uint32_t tape_count,
+                    const mh_assign* as, uint64_t row_first, uint64_t row_count,
+                    uint64_t index_base, uint32_t k, uint64_t* hits, uint32_t* n_hits,
+                    uint64_t* hit_count, uint32_t n_cols, uint32_t* rows_out) {
+    if (int32_t r = check_hits_args(ctx, ts, tape_first, tape_count, as, row_first, row_count, k,
+                                    hits, n_hits, n_cols, rows_out, "mh_run_hits"))
+        return r;
+    HitsPlan hp;
+    if (int32_t r = hits_plan(ctx, ts, tape_first, tape_count, as, row_count, k, n_cols, &hp))
+        return r;
+    return hits_submit(ctx, ts, tape_first, tape_count, as, row_first, row_count, index_base, k, hp,
+                       hits, n_hits, hit_count, n_cols, rows_out);
+}
+
+int32_t mh_assign_scatter(mh_assign* as, uint64_t first, uint32_t n_rows, const uint32_t* cols,
+                          uint32_t n_cols, const uint32_t* values) {
+    if (int32_t r = check_scatter_args(as, first, n_rows, cols, n_cols, values, "mh_assign_scatter"))
+        return r;
+    return scatter_queue(as, first, n_rows, cols, n_cols, values);
+}
+
+int32_t mh_query_round_hits(mh_ctx* ctx, const mh_tapeset* ts, mh_assign* as, const mh_guide* guide,
+                            uint64_t seed, uint64_t global_base, uint64_t count,
+                            uint32_t tape_first, uint32_t tape_count, const mh_spares* spares,
+                            uint32_t k, uint64_t* hits, uint32_t* n_hits, uint64_t* hit_count,
+                            uint32_t n_cols, uint32_t* rows_out) {
+    if (int32_t r = check_hits_args(ctx, ts, tape_first, tape_count, as, 0, count, k, hits, n_hits,
+                                    n_cols, rows_out, "mh_query_round_hits"))
+        return r;
+    if (!guide) return set_err(MH_E_INVALID, "mh_query_round_hits: null guide");
+    if (spares) {
+        if (spares->n_rows > count)
+            return set_err(MH_E_INVALID, "mh_query_round_hits: spares->n_rows beyond count");
+        if (int32_t r = check_scatter_args(as, 0, spares->n_rows, spares->cols, spares->n_cols,
+                                           spares->values, "mh_query_round_hits: spares"))
+            return r;
+    }
+    GuideLayout L;
+    if (int32_t r = check_guide(as, guide, &L)) return r;
+    HitsPlan hp;
+    if (int32_t r = hits_plan(ctx, ts, tape_first, tape_count, as, count, k, n_cols, &hp)) return r;
+    // the generator, the scatter, the run and the copy queue back to back: one host sync
+    if (int32_t r = mh_assign_generate_guided(as, seed, global_base, 0, count, guide)) return r;
+    if (spares)
+        if (int32_t r = scatter_queue(as, 0, spares->n_rows, spares->cols, spares->n_cols,
+                                      spares->values))
+            return r;
+    return hits_submit(ctx, ts, tape_first, tape_count, as, 0, count, global_base, k, hp, hits,
+                       n_hits, hit_count, n_cols, rows_out);
 }
 
 }  // extern "C"

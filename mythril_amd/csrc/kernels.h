@@ -156,6 +156,23 @@ hipError_t launch_mutate(const uint32_t* src, uint64_t src_stride, uint32_t* dst
                          uint64_t base, const KGuide& g, const uint32_t* set_conj,
                          const uint32_t* conj_col_off, const uint32_t* conj_cols,
                          hipStream_t stream);
+// hit listing (hits.hip; include/mythril_hip.h mh_run_hits).  masks[tape][wave] are a masks-mode
+// run's over row_count rows (mask_base = the first tape), `stride` its sieve_mask_stride.  Per tape:
+// hits[tape][0..k) = the min(k, hits) smallest satisfying rows as index0 + row of the run,
+// ascending, MH_NO_HIT after them; n_hits[tape] = how many are listed; hit_count[tape] = all of them
+hipError_t launch_hits_select(const unsigned long long* masks, uint64_t stride, uint32_t n_tapes,
+                              uint32_t row_count, uint64_t index0, uint32_t k, uint64_t* hits,
+                              uint32_t* n_hits, uint64_t* hit_count, hipStream_t stream);
+// out[tape][slot][w] = column word w (column w / 8, limb w % 8) of the buffer row
+// hits[tape][slot] - index_base, zero for a slot without a hit (launch_witness_rows per slot)
+hipError_t launch_hits_rows(const uint32_t* assign, uint64_t stride, const uint64_t* hits,
+                            uint32_t n_tapes, uint32_t k, uint64_t index_base, uint32_t n_cols,
+                            uint32_t* out, hipStream_t stream);
+// values[r][c][0..7] (device) into column cols[c] (device) of buffer row first + r; the caller has
+// checked the columns and the row range against the buffer
+hipError_t launch_scatter(uint32_t* assign, uint64_t stride, uint64_t first, uint32_t n_rows,
+                          const uint32_t* cols, uint32_t n_cols, const uint32_t* values,
+                          hipStream_t stream);
 hipError_t launch_microbench(uint32_t kind, uint32_t iters, uint32_t blocks, uint32_t* sink,
                              hipStream_t stream);
 

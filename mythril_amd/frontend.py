@@ -87,7 +87,8 @@ def configure(*, fallback: Optional[Callable] = None, verify: Optional[Callable]
     ``certify_resident=True`` (or SIEVE_CERTIFY_RESIDENT=1) does so through the sieve's resident
     Certifier, which keeps a path's compiled constraints between queries.
     ``decide`` (or SIEVE_DECIDE) says what a query the sieve decided UNSAT by enumeration becomes
-    (decide_mode); the decisions themselves are switched on by the sieve option ``decide_rows``."""
+    (decide_mode); the decisions themselves are switched on by the sieve option ``decide_rows``.
+    Sieve options (``rows``, ``spares``, ...) are further keywords, or one dict ``sieve_kwargs``."""
     if decide is not None:
         if decide not in (True, False, "audit"):
             raise ValueError("decide must be True, False or 'audit'")
@@ -108,6 +109,9 @@ def configure(*, fallback: Optional[Callable] = None, verify: Optional[Callable]
         _config["to_terms"] = to_terms
     if enabled is not None:
         _config["enabled"] = enabled
+    nested = sieve_kwargs.pop("sieve_kwargs", None)  # the options as one dict, as _config keeps them
+    if nested:
+        sieve_kwargs.update(nested)
     if sieve_kwargs:
         _config["sieve_kwargs"] = dict(sieve_kwargs)
         close_sieve()
@@ -193,12 +197,22 @@ def sieve():
     return s
 
 
+def _forget(s, key) -> None:
+    """A rejected witness leaves the sieve, with the spare models stored beside it."""
+    forget = getattr(s, "forget", None)
+    if forget is not None:
+        forget(key)
+    else:  # a stand-in without the method
+        s.witnesses.pop(key, None)
+
+
 def forget_witnesses() -> None:
     """Drop the sieve's parent-witness table (its keys are node ids of a term context the
     importer has just replaced)."""
     s = getattr(_tls, "sieve", None)
     if s is not None:
         s.witnesses.clear()
+        getattr(s, "spare_witnesses", {}).clear()
     clear_prefetched()  # (keyed by the same node ids)
 
 
@@ -384,7 +398,7 @@ def _certify_parked(s, fresh) -> dict:
     for (key, (ctx, _, _, _)), v in zip(found, got):
         out[key] = (ctx, v)
         if not isinstance(v, Exception) and not v:
-            s.witnesses.pop(key, None)  # does not seed the query's children
+            _forget(s, key)  # does not seed the query's children
     return out
 
 
@@ -469,7 +483,7 @@ def sieve_model(constraints, timeout_ms: Optional[float] = None):
             if verdict is not False:
                 log.debug("sieve witness rejected by certification: %r", verdict)
             stats.sieve_rejected += 1
-            s.witnesses.pop(key, None)
+            _forget(s, key)
             return None
     verify = _config["verify"]
     if verify is not None:

@@ -154,7 +154,15 @@ SIGNATURES = {
     "mh_assign_enumerate": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64]),
     "mh_query_enumerate": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32,
                                        C.c_uint32, _u64p, _u64p, C.c_uint32, _u32p]),
+    "mh_run_hits": (C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint64,
+                                C.c_uint64, C.c_uint32, _u64p, _u32p, _u64p, C.c_uint32, _u32p]),
+    "mh_assign_scatter": (C.c_int32, [_vp, C.c_uint64, C.c_uint32, _u32p, C.c_uint32, _u32p]),
+    "mh_query_round_hits": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64,
+                                        C.c_uint32, C.c_uint32, _vp, C.c_uint32, _u64p, _u32p,
+                                        _u64p, C.c_uint32, _u32p]),
 }
+HITS_MAX = 64          # MH_HITS_MAX
+HITS_MAX_ROWS = 65536  # MH_HITS_MAX_ROWS
 
 # mh_smt_record / mh_smt_result (include/mythril_hip.h)
 SMT_RECORD_DTYPE = np.dtype([("op", "u1"), ("pad0", "u1"), ("pad1", "<u2"), ("width", "<u4"),
@@ -1107,6 +1115,14 @@ class Assignments:
         _check(self.ctx.lib.mh_assign_generate_guided(self.h, seed, global_base, first, count,
                                                       C.byref(g)))
 
+    def scatter(self, first: int, cols: Sequence[int], values: np.ndarray) -> None:
+        """values u32 [n_rows, len(cols), 8] into columns `cols` (strictly ascending) of rows
+        [first, first + n_rows); the rows' other columns keep their content
+        (mh_assign_scatter; queued on the ctx stream)."""
+        cols, values = _scatter_arrays(cols, values)
+        _check(self.ctx.lib.mh_assign_scatter(self.h, first, values.shape[0], _ptr(cols),
+                                              len(cols), _ptr(values)))
+
     def enumerate(self, domains: "Domains", global_base: int = 0, first: int = 0,
                   count: Optional[int] = None) -> None:
         """Rows [first, first+count) get rows global_base.. of the domains' cross product
@@ -1168,6 +1184,61 @@ def query_round(ctx: Context, tapes: CompiledTapes, assign: "Assignments", guide
                                   global_base, count, tape_first, tc, mode, _ptr(fh, C.c_uint64),
                                   _ptr(hc, C.c_uint64), n_cols, _ptr(rows)))
     return fh[:tc], hc[:tc], rows[:tc, :n_cols]
+
+
+class Spares(C.Structure):
+    """mh_spares"""
+    _fields_ = [("n_rows", C.c_uint32), ("n_cols", C.c_uint32), ("cols", _u32p),
+                ("values", _u32p)]
+
+
+def _scatter_arrays(cols: Sequence[int], values: np.ndarray):
+    cols = np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
+    values = np.ascontiguousarray(values, dtype=np.uint32)
+    values = values.reshape(-1, len(cols), 8) if len(cols) else np.zeros((0, 0, 8), np.uint32)
+    return cols, values
+
+
+def _hits_out(tc: int, k: int, n_cols: int):
+    k1 = max(k, 1)
+    return (np.zeros((max(tc, 1), k1), dtype=np.uint64), np.zeros(max(tc, 1), dtype=np.uint32),
+            np.zeros(max(tc, 1), dtype=np.uint64),
+            np.zeros((max(tc, 1), k1, max(n_cols, 1), 8), dtype=np.uint32))
+
+
+def run_hits(ctx: Context, tapes: CompiledTapes, assign: Assignments, k: int, n_cols: int, *,
+             tape_first: int = 0, tape_count: Optional[int] = None, row_first: int = 0,
+             row_count: Optional[int] = None, index_base: int = 0):
+    """The k smallest satisfying rows of every tape (mh_run_hits): (hits [T, k] u64 global
+    indices ascending, NO_HIT after the listed ones; n_hits [T] u32; hit_count [T] u64;
+    rows [T, k, n_cols, 8] u32, zero for a slot without a hit)."""
+    tc = tapes.n_tapes - tape_first if tape_count is None else tape_count
+    rc = assign.capacity - row_first if row_count is None else row_count
+    hits, nh, hc, rows = _hits_out(tc, k, n_cols)
+    _check(ctx.lib.mh_run_hits(ctx.h, tapes.h, tape_first, tc, assign.h, row_first, rc, index_base,
+                               k, _ptr(hits, C.c_uint64), _ptr(nh), _ptr(hc, C.c_uint64), n_cols,
+                               _ptr(rows)))
+    return hits[:tc], nh[:tc], hc[:tc], rows[:tc, :, :n_cols]
+
+
+def query_round_hits(ctx: Context, tapes: CompiledTapes, assign: "Assignments",
+                     guide: GuideHandle, seed: int, global_base: int, count: int, n_cols: int,
+                     k: int, *, spares=None, tape_first: int = 0,
+                     tape_count: Optional[int] = None):
+    """One guided round with a listing (mh_query_round_hits): rows [0, count) generated from
+    `guide`; `spares` = (cols, values [n, len(cols), 8]) scattered over rows [0, n); then
+    run_hits over the rows with index_base = global_base.  Returns run_hits' tuple."""
+    tc = tapes.n_tapes - tape_first if tape_count is None else tape_count
+    hits, nh, hc, rows = _hits_out(tc, k, n_cols)
+    sp = None
+    if spares is not None:
+        cols, values = _scatter_arrays(*spares)
+        sp = C.byref(Spares(values.shape[0], len(cols), _ptr(cols), _ptr(values)))
+    _check(ctx.lib.mh_query_round_hits(ctx.h, tapes.h, assign.h, C.byref(guide.guide), seed,
+                                       global_base, count, tape_first, tc, sp, k,
+                                       _ptr(hits, C.c_uint64), _ptr(nh), _ptr(hc, C.c_uint64),
+                                       n_cols, _ptr(rows)))
+    return hits[:tc], nh[:tc], hc[:tc], rows[:tc, :, :n_cols]
 
 
 def query_round_many(ctx: Context, jobs: Sequence[dict]):

@@ -45,6 +45,8 @@ class Witness:
     index: int = 0                     # global candidate index that satisfied the query
     rounds: int = 0
     repaired: bool = False             # a group's row came from the repair step (Sieve._repair)
+    # further models of the query found beside it (Sieve(spares=K)): the query's columns only
+    spares: List[Dict[str, int]] = field(default_factory=list)
 
 
 @dataclass
@@ -446,7 +448,7 @@ class Sieve:
                  native_query: bool = True, second_round: Optional[str] = None,
                  keccak_second_chance: Optional[bool] = None, repair_rounds: int = 0,
                  repair_elites: Optional[int] = None, repair_children: Optional[int] = None,
-                 decide_rows: int = 0):
+                 decide_rows: int = 0, spares: int = 0):
         self.ctx = native.Context(device)
         # host stages by the native query compiler (csrc/query.cpp); False: the Python stages
         # (lower.py, buckets, local_tapeset) it is checked against (tests/test_query_native.py)
@@ -509,6 +511,13 @@ class Sieve:
         self.stats = SieveStats()
         self.witnesses: "OrderedDict[tuple, Dict[str, int]]" = OrderedDict()
         self.max_witnesses = 1 << 14
+        # spare witnesses: with spares = K > 0 every guided round of a sequential
+        # query lists its K smallest hits per group (native.query_round_hits), a solved query
+        # keeps up to K - 1 further models beside its witness, and a query's first round tries its
+        # nearest ancestor's witness and spares as its first rows.  0 (the default) runs none of
+        # it.  SIEVE_SPARES overrides.
+        self.spares = min(native.HITS_MAX, max(0, int(os.environ.get("SIEVE_SPARES", spares))))
+        self.spare_witnesses: "OrderedDict[tuple, List[Dict[str, int]]]" = OrderedDict()
         # the last query this sieve missed after a device round, (key, schema): a model the
         # fallback then finds for it is learnt as its witness (learn)
         # (key, schema[, the keccak second chance's schema])
@@ -606,13 +615,26 @@ class Sieve:
         return self.assign
 
     def remember(self, key: tuple, w: Witness) -> None:
-        self._store(key, w.values)
+        self._store(key, w.values, w.spares)
 
-    def _store(self, key: tuple, values: Dict[str, int]) -> None:
+    def _store(self, key: tuple, values: Dict[str, int],
+               spares: Optional[List[Dict[str, int]]] = None) -> None:
         self.witnesses[key] = values
         self.witnesses.move_to_end(key)
+        if spares:
+            self.spare_witnesses[key] = spares
+            self.spare_witnesses.move_to_end(key)
+        else:  # (a learnt model, or a witness found alone, replaces one that had spares)
+            self.spare_witnesses.pop(key, None)
         while len(self.witnesses) > self.max_witnesses:
-            self.witnesses.popitem(last=False)
+            old, _ = self.witnesses.popitem(last=False)
+            self.spare_witnesses.pop(old, None)
+
+    def forget(self, key: tuple) -> None:
+        """Drop a query's witness and its spares (a witness the verifier or certifier rejected
+        does not seed the query's children)."""
+        self.witnesses.pop(key, None)
+        self.spare_witnesses.pop(key, None)
 
     def learn(self, key: tuple, value_of: Callable[[Column], Optional[int]], ctx=None,
               value_at: Optional[Callable[[Column, int], Optional[int]]] = None) -> int:
@@ -1127,6 +1149,55 @@ class Sieve:
                 return w, (root_ends[j - 1] if j - 1 < len(root_ends) else 0)
         return None, 0
 
+    def _ancestor_key(self, key: Optional[tuple]) -> Optional[tuple]:
+        """The key _ancestor's witness is stored under, or None."""
+        if not key:
+            return None
+        for j in range(len(key) - 1, max(len(key) - 1 - self.ANCESTORS, 0), -1):
+            if key[:j] in self.witnesses:
+                return key[:j]
+        return None
+
+    def _spare_rows(self, key: Optional[tuple], parent, col_index: Dict[str, int], n: int):
+        """The rows a query's first round tries first: its ancestor's witness, then the ancestor's
+        spares, over the columns every one of them and the query have -- (column numbers
+        ascending, values u32 [rows, columns, 8]) -- or None when the ancestor has no spares.
+        At most `n` rows (the round's)."""
+        pk = self._ancestor_key(key)
+        extra = self.spare_witnesses.get(pk) if pk is not None else None
+        if not extra or not parent or self.witnesses.get(pk) is not parent:
+            return None
+        rows = ([parent] + list(extra))[:n]
+        names = [c for c in col_index if all(c in r for r in rows)]
+        if not names:
+            return None
+        names.sort(key=col_index.__getitem__)
+        vals = np.zeros((len(rows), len(names), 8), dtype=np.uint32)
+        for i, r in enumerate(rows):
+            raw = b"".join((int(r[c]) & ((1 << 256) - 1)).to_bytes(32, "little") for c in names)
+            vals[i] = np.frombuffer(raw, dtype="<u4").reshape(len(names), 8)
+        return np.array([col_index[c] for c in names], dtype=np.uint32), vals
+
+    @staticmethod
+    def _composite_spares(columns, group_cols, values: Dict[str, int], ghits, k: int
+                          ) -> List[Dict[str, int]]:
+        """A solved query's spares: spare j (1 <= j < k) takes from every group g its hit
+        j mod n_hits_g (a group solved by one row contributes that row); the query's columns
+        only, a column no conjunct reads at 0 as in the witness.  Spares equal to the witness or
+        to an earlier spare are dropped."""
+        lists = []
+        for g, cols in enumerate(group_cols):
+            lists.append(ghits[g] if ghits[g] else [{columns[c]: values[columns[c]] for c in cols}])
+        base = {c: values[c] for c in columns}
+        out: List[Dict[str, int]] = []
+        for j in range(1, k):
+            row = {c: 0 for c in columns}
+            for rows in lists:
+                row.update(rows[j % len(rows)])
+            if row != base and row not in out:
+                out.append(row)
+        return out
+
     def _parent_kreads(self, b: TapeBuilder, schema: Schema, base_schema: Schema,
                        parent: Dict[str, int]) -> Dict[str, int]:
         """The parent's witness with the keccak read columns of `schema` (the second chance's
@@ -1253,6 +1324,10 @@ class Sieve:
             assign = self._buffer(len(columns)) if first is None else None
             values: Dict[str, int] = {}
             solved = [False] * len(group_cols)
+            # spare witnesses: a sequential query's guided rounds list K hits per group
+            use_hits = self.spares > 0 and first is None
+            ghits: List[Optional[List[Dict[str, int]]]] = [None] * len(group_cols)
+            n_sp = 0
             first_index = None
             last_n = 0
             offset = (1 << 23) if keccak_reads else 0
@@ -1305,6 +1380,7 @@ class Sieve:
                 # a later round runs only the tapes from the first to the last unsolved group
                 g0 = solved.index(False)
                 g1 = len(solved) - solved[::-1].index(False)
+                hrows = nh = None
                 if rnd == 0 and first is not None:
                     fh, wrows = first[0], first[1]  # run by solve_many's batched round
                 else:
@@ -1312,14 +1388,29 @@ class Sieve:
                         assign = self._buffer(len(columns))
                     # generator, run, and the first witnesses with their rows' columns in one call
                     # and one copy back (mh_query_round)
-                    fh, _, wrows = native.query_round(self.ctx, ct, assign, round_guide, self.seed,
-                                                      base, n, len(columns), tape_first=g0,
-                                                      tape_count=g1 - g0,
-                                                      mode=native.MODE_FIRST_HIT)
+                    if use_hits:
+                        # the same round with the K smallest hits of every group listed
+                        # (mh_query_round_hits); hit 0 is the witness's row as below.  The first
+                        # round's first rows are the ancestor's witness and spares
+                        sp = self._spare_rows(key, parent, col_index, n) if rnd == 0 else None
+                        n_sp = len(sp[1]) if sp is not None else 0
+                        if rnd == 0:
+                            st.extra["spare_rows"] = st.extra.get("spare_rows", 0) + n_sp
+                            self.last_rounds["spares"] = n_sp
+                            self.last_rounds["spare_hit"] = 0
+                        hh, nh, _, hrows = native.query_round_hits(
+                            self.ctx, ct, assign, round_guide, self.seed, base, n, len(columns),
+                            self.spares, spares=sp, tape_first=g0, tape_count=g1 - g0)
+                        fh, wrows = hh[:, 0], hrows[:, 0]
+                    else:
+                        fh, _, wrows = native.query_round(
+                            self.ctx, ct, assign, round_guide, self.seed, base, n, len(columns),
+                            tape_first=g0, tape_count=g1 - g0, mode=native.MODE_FIRST_HIT)
                     tr = time.perf_counter()
                     st.add("run", tr - tb)
                 self.stats.rounds += 1
                 self.stats.rows += n
+                fresh = []  # the groups this round solves
                 for i, hit in enumerate(fh.tolist()):
                     g = g0 + i
                     if solved[g] or hit == native.NO_HIT:
@@ -1329,7 +1420,20 @@ class Sieve:
                     for c in group_cols[g]:
                         values[columns[c]] = int.from_bytes(raw[32 * c:32 * c + 32], "little")
                     solved[g] = True
+                    fresh.append(hit)
                     first_index = hit if first_index is None else min(first_index, hit)
+                    if use_hits and hrows is not None:
+                        ghits[g] = []
+                        for j in range(int(nh[i])):
+                            raw = np.ascontiguousarray(hrows[i, j], dtype="<u4").tobytes()
+                            ghits[g].append({
+                                columns[c]: int.from_bytes(raw[32 * c:32 * c + 32], "little")
+                                for c in group_cols[g]})
+                if (use_hits and rnd == 0 and n_sp and all(solved)
+                        and len(fresh) == len(solved) and max(fresh) < base + n_sp):
+                    # every group answered by one of the ancestor's rows
+                    st.extra["spare_hits"] = st.extra.get("spare_hits", 0) + 1
+                    self.last_rounds["spare_hit"] = 1
                 if all(solved):
                     for c in columns:  # columns no conjunct reads: any value is a model
                         values.setdefault(c, 0)
@@ -1341,7 +1445,11 @@ class Sieve:
                         st.add("definitions", time.perf_counter() - td)
                     if rnd and inc_ok:
                         st.extra["inc_hits"] = st.extra.get("inc_hits", 0) + 1
-                    return Witness(schema, values, first_index, rnd + 1), schema, False
+                    w = Witness(schema, values, first_index, rnd + 1)
+                    if use_hits:
+                        w.spares = self._composite_spares(columns, group_cols, values, ghits,
+                                                          self.spares)
+                    return w, schema, False
                 if time.perf_counter() - t0 > budget:
                     break
             if (self.repair_rounds > 0 and last_n and not all(solved)
@@ -1368,8 +1476,12 @@ class Sieve:
                         for (c, _), v in zip(defs, got):
                             values[c] = v
                         st.add("definitions", time.perf_counter() - td)
-                    return (Witness(schema, values, first_index, self.last_rounds["rounds"],
-                                    repaired=True), schema, False)
+                    w = Witness(schema, values, first_index, self.last_rounds["rounds"],
+                                repaired=True)
+                    if use_hits:
+                        w.spares = self._composite_spares(columns, group_cols, values, ghits,
+                                                          self.spares)
+                    return w, schema, False
             if self.decide_rows > 0 and s.decide is not None and not all(solved):
                 if assign is None:
                     assign = self._buffer(len(columns))
@@ -1390,8 +1502,11 @@ class Sieve:
                         for (c, _), v in zip(defs, got):
                             values[c] = v
                         st.add("definitions", time.perf_counter() - td)
-                    return (Witness(schema, values, first_index,
-                                    self.last_rounds.get("rounds", 0)), schema, False)
+                    w = Witness(schema, values, first_index, self.last_rounds.get("rounds", 0))
+                    if use_hits:
+                        w.spares = self._composite_spares(columns, group_cols, values, ghits,
+                                                          self.spares)
+                    return w, schema, False
             kec = any(not solved[g] and _reads_keccak(ts.tapes[g].nodes)
                       for g in range(len(solved)))
             return None, schema, kec

@@ -24,18 +24,20 @@ behaviour is kept on every error (SURVEY.md §5 "fail closed").
 from __future__ import annotations
 
 import os
+import re
 import threading
 import time
 from collections import OrderedDict
+from copy import deepcopy
 from dataclasses import dataclass, field
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import decide, native
-from .lower import (Column, KeccakMap, LoweringUnsupported, Schema, cell_name, lower_query,
-                    node_columns)
-from .tape import NODE_DTYPE, Op, Tape, TapeBuilder, TapeError, TapeSet
+from .lower import (Column, KeccakMap, Lowering, LoweringUnsupported, Schema, cell_name,
+                    lower_query, node_columns)
+from .tape import ARITY, NODE_DTYPE, Op, Tape, TapeBuilder, TapeError, TapeSet
 
 
 @dataclass
@@ -66,6 +68,10 @@ class SieveStats:
 
     def add(self, stage: str, dt: float) -> None:
         self.stage_s[stage] = self.stage_s.get(stage, 0.0) + dt
+
+    def bump(self, name: str, n: int = 1) -> None:
+        """Count `n` more of `extra[name]` (the key appears with its first bump, even of 0)."""
+        self.extra[name] = self.extra.get(name, 0) + n
 
 
 def local_tape(b: TapeBuilder, root: int, columns: Sequence[str]) -> np.ndarray:
@@ -124,7 +130,35 @@ def local_tapeset(b: TapeBuilder, roots: Sequence[int], columns: Sequence[str]) 
     return ts
 
 
-REFUTED = object()  # _host_native's answer for a query that contradicts itself
+REFUTED = object()  # what a refuted query has in place of a schema (_attempt, last_miss)
+
+
+class _Host(NamedTuple):
+    """A query after _host_native / _host_python: its lowering, groups and tapes."""
+    columns: Sequence[str]
+    widths: Sequence[int]
+    schema: Schema
+    root_nodes: np.ndarray  # the root's tape, which the guide is harvested from
+    ts: TapeSet             # one tape per group
+    group_cols: Sequence[Sequence[int]]
+    defs: list
+    root_ends: Sequence[int]
+    # what decide.eligible reads of a natively built query: (keccak reads?, keccak table?, column
+    # kinds); None: never decided (the Python host stages, or decide_rows = 0)
+    decide: Optional[tuple] = None
+    refuted = False
+
+
+class _Refuted:
+    """_host_native's and _stage's answer for a query that contradicts itself: no device round.
+    ``unsat``: every group was eligible for the decision step, so the query is decided UNSAT."""
+    refuted = True
+
+    def __init__(self, unsat: bool):
+        self.unsat = unsat
+
+    def close(self) -> None:
+        pass
 
 
 class NativeDefs(list):
@@ -183,8 +217,6 @@ def substitute(b: TapeBuilder, root: int, env: Dict[int, int]) -> int:
     nodes above the replaced ones; hash-consing shares everything else)."""
     nodes, out = b.nodes, {}
     st = [root]
-    from .tape import ARITY
-
     while st:
         n = st[-1]
         if n in out:
@@ -381,8 +413,6 @@ def rematerialize(nodes: np.ndarray, max_size: int) -> np.ndarray:
     calldata bytes in several overlapping words (calldata.py:48-54: word(0) and word(4) share 28
     byte terms), which otherwise holds more values live than the device register file has; the
     copies cost a few cheap instructions each."""
-    from .tape import ARITY
-
     n = len(nodes)
     ops = nodes["op"].astype(int)
     opnds = np.stack([nodes["a"], nodes["b"], nodes["c"]], axis=1).astype(int)
@@ -421,23 +451,96 @@ def rematerialize(nodes: np.ndarray, max_size: int) -> np.ndarray:
 class _Staged:
     """A query after its host stage (Sieve._stage), before its rounds (Sieve._rounds): the
     lowering, the parent witness it was harvested under, the kept guide and the compiled tapes."""
-
     __slots__ = ("b", "key", "keccak_reads", "base_schema", "qno", "host", "col_index", "parent",
-                 "parent_len", "guide", "ct", "t1", "decide")
+                 "parent_len", "guide", "ct", "t1")
+    refuted = False  # (_stage's other answer is a _Refuted)
 
     def __init__(self, b, key, keccak_reads, base_schema, qno, host, col_index, parent,
-                 parent_len, guide, ct, t1, decide=None):
+                 parent_len, guide, ct, t1):
         self.b, self.key, self.keccak_reads, self.base_schema = b, key, keccak_reads, base_schema
         self.qno, self.host, self.col_index = qno, host, col_index
         self.parent, self.parent_len, self.guide, self.ct, self.t1 = (parent, parent_len, guide,
                                                                       ct, t1)
-        # (keccak reads?, keccak table?, column kinds) of a natively built query, for the
-        # decision step's eligibility; None: never decided (the Python host stages)
-        self.decide = decide
 
     def close(self) -> None:  # a staged query whose rounds never ran
         self.ct.close()
         self.guide.close()
+
+
+def _row_values(row, columns: Sequence[str], cols: Sequence[int], out: Dict[str, int]):
+    """A witness row's values (32 little-endian bytes each) in the columns `cols`, by name, put
+    into `out`."""
+    raw = np.ascontiguousarray(row, dtype="<u4").tobytes()
+    for c in cols:
+        out[columns[c]] = int.from_bytes(raw[32 * c:32 * c + 32], "little")
+    return out
+
+
+class _Run:
+    """One staged query's rounds in progress (Sieve._rounds): what the rounds, the repair step
+    and the decision step read and fill.  ``first``: its first round's results when a batched
+    round has run it already (no round then lists spare hits)."""
+    __slots__ = ("sieve", "s", "first", "budget", "t0", "columns", "group_cols", "solved", "values",
+                 "ghits", "first_index", "use_hits", "buffer")
+
+    def __init__(self, sieve: "Sieve", s: _Staged, first, budget: float, t0: float):
+        self.sieve, self.s, self.first, self.budget, self.t0 = sieve, s, first, budget, t0
+        self.columns, self.group_cols = s.host.columns, s.host.group_cols
+        self.solved = [False] * len(self.group_cols)
+        self.values: Dict[str, int] = {}
+        # spare witnesses: a sequential query's guided rounds list K hits per group
+        self.use_hits = sieve.spares > 0 and first is None
+        self.ghits: List[Optional[List[Dict[str, int]]]] = [None] * len(self.group_cols)
+        self.first_index: Optional[int] = None  # the smallest over rounds, repair and decide
+        self.buffer: Optional[native.Assignments] = None  # the sieve's, once a step needed it
+
+    def assign(self) -> native.Assignments:
+        if self.buffer is None:
+            self.buffer = self.sieve._buffer(len(self.columns))
+        return self.buffer
+
+    def spent(self) -> bool:
+        return time.perf_counter() - self.t0 > self.budget
+
+    def take(self, g: int, row, hit: int) -> None:
+        """Group `g` is answered by witness row `row`, candidate number `hit`."""
+        _row_values(row, self.columns, self.group_cols[g], self.values)
+        self.solved[g] = True
+        self.first_index = hit if self.first_index is None else min(self.first_index, hit)
+
+    def complete(self, rounds: int, repaired: bool = False) -> Witness:
+        """The witness of a query whose groups are all solved."""
+        sieve, host, values = self.sieve, self.s.host, self.values
+        for c in self.columns:  # columns no conjunct reads: any value is a model
+            values.setdefault(c, 0)
+        if host.defs:  # defined symbols take their terms' values under the row
+            td = time.perf_counter()
+            got = sieve.eval_definitions(self.s.b, host.defs, self.columns, values)
+            for (c, _), v in zip(host.defs, got):
+                values[c] = v
+            sieve.stats.add("definitions", time.perf_counter() - td)
+        w = Witness(host.schema, values, self.first_index, rounds, repaired=repaired)
+        if self.use_hits:
+            w.spares = self.spares(sieve.spares)
+        return w
+
+    def spares(self, k: int) -> List[Dict[str, int]]:
+        """A solved query's spares: spare j (1 <= j < k) takes from every group g its hit
+        j mod n_hits_g (a group solved by one row contributes that row); the query's columns
+        only, a column no conjunct reads at 0 as in the witness.  Spares equal to the witness or
+        to an earlier spare are dropped."""
+        columns, values = self.columns, self.values
+        lists = [self.ghits[g] or [{columns[c]: values[columns[c]] for c in cols}]
+                 for g, cols in enumerate(self.group_cols)]
+        base = {c: values[c] for c in columns}
+        out: List[Dict[str, int]] = []
+        for j in range(1, k):
+            row = {c: 0 for c in columns}
+            for rows in lists:
+                row.update(rows[j % len(rows)])
+            if row != base and row not in out:
+                out.append(row)
+        return out
 
 
 class Sieve:
@@ -561,9 +664,6 @@ class Sieve:
         # the last query was decided UNSAT: an eligible group has no row, or the host refuted an
         # eligible query.  Cleared per query; solve() still returns None.
         self.last_unsat = False
-        self._refuted_unsat: set = set()  # numbers of refuted queries that were eligible
-        self._decide_info = None          # the last native host stage's (keccak table?, kinds)
-        self._refuted_eligible = False
         self.repairer = None                                  # native.Repair, made on first use
         self.assign2: Optional[native.Assignments] = None     # the children's buffer
         # solve_many: first-round buffers (first_rows rows) by column capacity, kept between
@@ -603,15 +703,17 @@ class Sieve:
             self.guides_kr.close()
         self.ctx.close()
 
+    @staticmethod
+    def _col_capacity(n_cols: int) -> int:
+        """The column capacity of a buffer for `n_cols` columns: a power of two, 64 at least."""
+        return 1 << (max(n_cols, 64) - 1).bit_length()
 
     def _buffer(self, n_cols: int) -> native.Assignments:
         rows = max(self.first_rows, (self.max_rounds - 1) * self.rows)
         if self.assign is None or self.assign.n_vars < n_cols or self.assign.capacity < rows:
             if self.assign is not None:
                 self.assign.close()
-            cap = max(n_cols, 64)
-            cap = 1 << (cap - 1).bit_length()
-            self.assign = self.ctx.assignments(cap, rows)
+            self.assign = self.ctx.assignments(self._col_capacity(n_cols), rows)
         return self.assign
 
     def remember(self, key: tuple, w: Witness) -> None:
@@ -668,7 +770,7 @@ class Sieve:
             self._learn_reads(lm[1:], values, ctx, value_at)
         if values:
             self._store(key, values)
-            self.stats.extra["learnt"] = self.stats.extra.get("learnt", 0) + 1
+            self.stats.bump("learnt")
         return len(values)
 
     def _learn_reads(self, schemas, values: Dict[str, int], ctx, value_at) -> None:
@@ -707,10 +809,6 @@ class Sieve:
     def compile(self, ts: TapeSet) -> native.CompiledTapes:
         """Compile a query's tapes; a tape that runs out of registers is retried with cheap
         sub-terms duplicated at their uses (rematerialize), widening what counts as cheap."""
-        import re
-
-        from .tape import Tape
-
         orig = [t.nodes for t in ts.tapes]
         level = [0] * len(orig)
         sizes = (0, 8, 32, 256)
@@ -727,8 +825,7 @@ class Sieve:
                     raise
                 ts.tapes[t] = Tape(rematerialize(orig[t], sizes[level[t]]))
                 ts.flat = None  # the tapes no longer lie back to back
-                k = "remat_%d" % sizes[level[t]]
-                self.stats.extra[k] = self.stats.extra.get(k, 0) + 1
+                self.stats.bump("remat_%d" % sizes[level[t]])
 
     def _count_spills(self, ct: native.CompiledTapes) -> native.CompiledTapes:
         """Counts the tapes whose live values exceed the interpreter's registers: they compile
@@ -736,7 +833,7 @@ class Sieve:
         spills = getattr(ct, "spills", None)  # (a stand-in context's tapes have none)
         n = int(np.count_nonzero(spills())) if spills is not None else 0
         if n:
-            self.stats.extra["spilled_tapes"] = self.stats.extra.get("spilled_tapes", 0) + n
+            self.stats.bump("spilled_tapes", n)
         return ct
 
     @staticmethod
@@ -762,7 +859,7 @@ class Sieve:
         rest, defs = eliminate_definitions(b, conj, schema)
         if not defs:
             return root, []
-        self.stats.extra["definitions"] = self.stats.extra.get("definitions", 0) + len(defs)
+        self.stats.bump("definitions", len(defs))
         if not rest:
             return b.true(), defs
         acc = rest[0]
@@ -819,7 +916,7 @@ class Sieve:
     def _host_native(self, b: TapeBuilder, roots: Sequence[int], keccak_reads: bool = False):
         """The host stages by the native query compiler (mh_query_build: lowering, groups and
         tapes in one call, csrc/query.cpp); None for a query with a candidate definition (those
-        take _host_python, whose eliminate_definitions solves for the symbol); REFUTED for a
+        take _host_python, whose eliminate_definitions solves for the symbol); a _Refuted for a
         conjunction that contradicts itself syntactically (MH_QUERY_REFUTED: x == 1 and x == 2,
         p and not p, bounds with an empty range), which no row can satisfy."""
         t0 = time.perf_counter()
@@ -829,23 +926,22 @@ class Sieve:
         except native.Unsupported:
             # a shape the native compiler refuses (a variable named like an array cell, ...):
             # the Python stages it restates may still take it
-            st.extra["native_unsupported"] = st.extra.get("native_unsupported", 0) + 1
+            st.bump("native_unsupported")
             st.add("lower", time.perf_counter() - t0)
             return None
         st.add("lower", time.perf_counter() - t0)
-        if self.decide_rows > 0:  # what eligibility reads (decide.eligible), for _stage
-            self._decide_info = (keccak_reads, cq.has_keccak_table(), cq.column_kinds())
+        dinfo = ((keccak_reads, cq.has_keccak_table(), cq.column_kinds())
+                 if self.decide_rows > 0 else None)  # what eligibility reads (decide.eligible)
         if cq.flags & native.QUERY_REFUTED:
-            st.extra["refuted"] = st.extra.get("refuted", 0) + 1
+            st.bump("refuted")
             # the refuted conjunction is the lowered one: it stands for the caller's only when
             # every group is eligible (none of the query's columns or tapes touches keccak)
-            self._refuted_eligible = self.decide_rows > 0 and decide.eligible(
-                *self._decide_info, range(len(cq.names)), cq.nodes)
-            return REFUTED
+            return _Refuted(dinfo is not None and decide.eligible(
+                *dinfo, range(len(cq.names)), cq.nodes))
         columns = cq.names
         defs = []
         if cq.flags & native.QUERY_DEFINITIONS:  # solved for the defined symbols natively
-            st.extra["definitions"] = st.extra.get("definitions", 0) + len(cq.defs)
+            st.bump("definitions", len(cq.defs))
             defs = NativeDefs([(columns[c], t) for c, t in zip(cq.defs, cq.def_tapes)],
                               cq.consts)
         ts = TapeSet(columns)
@@ -857,9 +953,9 @@ class Sieve:
         off = np.asarray(cq.tape_off[k:], dtype=np.uint64)
         ts.flat = (cq.nodes[cq.tape_off[k]:cq.tape_off[-1]], off - off[0], cq.consts)
         if len(cq.groups) > 1:
-            st.extra["bucketed"] = st.extra.get("bucketed", 0) + 1
-        return (columns, cq.widths, NativeSchema(cq, keccak_reads), tapes[0], ts, cq.groups, defs,
-                [] if defs else cq.root_ends)
+            st.bump("bucketed")
+        return _Host(columns, cq.widths, NativeSchema(cq, keccak_reads), tapes[0], ts, cq.groups,
+                     defs, [] if defs else cq.root_ends, dinfo)
 
     def _host_python(self, b: TapeBuilder, roots: Sequence[int], keccak_reads: bool = False):
         """The host stages in Python: lower_query, definitions, buckets, local tapes."""
@@ -872,8 +968,6 @@ class Sieve:
         if not columns:  # ground query: one row decides it
             columns = ["__ground__"]
             b.var("__ground__", 1)
-            from .lower import Column
-
             schema.columns["__ground__"] = Column("__ground__", 1, "var", "__ground__")
         root, defs = self.solve_definitions(b, root, schema)
         groups = self.bucket_roots(b, root)
@@ -890,10 +984,10 @@ class Sieve:
             ts = local_tapeset(b, [root] + accs, columns)
             root_nodes = ts.tapes.pop(0).nodes
         if len(groups) > 1:
-            st.extra["bucketed"] = st.extra.get("bucketed", 0) + 1
+            st.bump("bucketed")
         st.add("tapes", time.perf_counter() - t_l)
         widths = [schema.columns[c].width for c in columns]
-        return columns, widths, schema, root_nodes, ts, group_cols, defs, []
+        return _Host(columns, widths, schema, root_nodes, ts, group_cols, defs, [])
 
     @classmethod
     def buckets(cls, b: TapeBuilder, root: int) -> List[Tuple[List[int], set]]:
@@ -935,18 +1029,17 @@ class Sieve:
         a batched round (solve_many) has run it already."""
         st = self.stats
         self.last_unsat = False
-        if staged is REFUTED:
+        if staged.refuted:
             w, schema, kec = None, REFUTED, False
-            if qno in self._refuted_unsat:
-                self._refuted_unsat.discard(qno)
+            if staged.unsat:
                 self.last_unsat = True
-                st.extra["decided_unsat"] = st.extra.get("decided_unsat", 0) + 1
+                st.bump("decided_unsat")
         else:
             w, schema, kec = self._rounds(staged, budget, t0, first)
         schema2 = None
         if (w is None and kec and self.keccak_second_chance
                 and time.perf_counter() - t0 < budget):
-            st.extra["keccak2_tries"] = st.extra.get("keccak2_tries", 0) + 1
+            st.bump("keccak2_tries")
             first_rounds = self.last_rounds
             try:
                 w, schema2, _ = self._attempt(b, roots, key, budget, t0, True,
@@ -954,11 +1047,11 @@ class Sieve:
             except (LoweringUnsupported, native.Unsupported):
                 # a shape the second lowering cannot take (register pressure of its larger
                 # tapes, ...): the first attempt's miss stands
-                st.extra["keccak2_unsupported"] = st.extra.get("keccak2_unsupported", 0) + 1
+                st.bump("keccak2_unsupported")
                 w = None
             self.last_rounds = dict(first_rounds, keccak2=int(w is not None))
             if w is not None:
-                st.extra["keccak2_hits"] = st.extra.get("keccak2_hits", 0) + 1
+                st.bump("keccak2_hits")
         if w is None:
             self.stats.misses += 1
             if schema is not REFUTED and key:
@@ -977,8 +1070,7 @@ class Sieve:
     def _pool_buffer(self, n_cols: int, taken: Dict[int, int]) -> native.Assignments:
         """A first-round buffer from the pool, of _buffer's column capacity; `taken` counts the
         ones this batch uses already."""
-        cap = max(n_cols, 64)
-        cap = 1 << (cap - 1).bit_length()
+        cap = self._col_capacity(n_cols)
         bufs = self.round_pool.setdefault(cap, [])
         k = taken.get(cap, 0)
         taken[cap] = k + 1
@@ -999,8 +1091,8 @@ class Sieve:
         every query that needs one run in one device submission (native.query_round_many)
         instead of one submission each.  Returns a witness or None per query; ``last_many`` has,
         per query, ``miss`` (what last_miss would have been), ``rounds`` (last_rounds), ``unsat``
-        (True for a query decided UNSAT, last_unsat; absent otherwise) and ``error`` (the exception an unsupported query raises from solve(), reported here instead:
-        it does not fail the list).
+        (True for a query decided UNSAT, last_unsat; absent otherwise) and ``error`` (the exception
+        an unsupported query raises from solve(), reported here instead: it does not fail the list).
 
         On Sieves created alike, the witnesses, their ``index`` and ``rounds``, the stats counters
         and the ``witnesses`` store are what calling solve() on the list in order gives:
@@ -1034,8 +1126,7 @@ class Sieve:
             j = i
             while j < n and len(seg) < self.BATCH_MAX:
                 k = keys[j]
-                if k and any(k[:m] in seg_keys
-                             for m in range(len(k) - 1, max(len(k) - 1 - self.ANCESTORS, 0), -1)):
+                if any(p in seg_keys for p in self._prefixes(k)):
                     break
                 if ident[j] in seen:
                     dups.append((j, seen[ident[j]]))
@@ -1061,14 +1152,14 @@ class Sieve:
                     except Exception as e:  # noqa: BLE001 - what solve() raises, per query
                         rec[q]["error"] = e
                 # 2. one submission for every first round
-                live = [q for q in seg if q in staged and staged[q] is not REFUTED]
+                live = [q for q in seg if q in staged and not staged[q].refuted]
                 firsts: Dict[int, tuple] = {}
                 if len(live) > 1:
                     taken: Dict[int, int] = {}
                     jobs = []
                     for q in live:
                         s = staged[q]
-                        n_cols = len(s.host[0])
+                        n_cols = len(s.host.columns)
                         jobs.append(dict(tapes=s.ct, assign=self._pool_buffer(n_cols, taken),
                                          guide=s.guide, seed=self.seed, global_base=s.qno << 24,
                                          count=self.first_rows, n_cols=n_cols,
@@ -1077,12 +1168,12 @@ class Sieve:
                     try:
                         res = native.query_round_many(self.ctx, jobs)
                     except native.SieveError:  # (a shape the batch refuses: one by one instead)
-                        st.extra["batch_refused"] = st.extra.get("batch_refused", 0) + 1
+                        st.bump("batch_refused")
                         res = None
                     st.add("run", time.perf_counter() - tb)
                     if res is not None:
-                        st.extra["batched_rounds"] = st.extra.get("batched_rounds", 0) + len(live)
-                        st.extra["batches"] = st.extra.get("batches", 0) + 1
+                        st.bump("batched_rounds", len(live))
+                        st.bump("batches")
                         for q, job, (fh, _, wrows) in zip(live, jobs, res):
                             firsts[q] = (fh, wrows, job["assign"])
                 # 3. every query's later rounds and accounting, in list order
@@ -1115,8 +1206,7 @@ class Sieve:
                         rec[q]["unsat"] = True
             finally:
                 for s in staged.values():  # an interrupted batch: nothing stays open
-                    if s is not REFUTED:
-                        s.close()
+                    s.close()
             i = j
         self.last_rounds = {}
         self.last_miss = None
@@ -1137,25 +1227,26 @@ class Sieve:
     # under the plugin a missed parent has the fallback's model learnt anyway
     ANCESTORS = int(os.environ.get("SIEVE_ANCESTORS", "1"))
 
+    def _prefixes(self, key: Optional[tuple]) -> Iterator[tuple]:
+        """The keys of the query's last ANCESTORS prefixes, the parent's first."""
+        n = len(key) if key else 0
+        for j in range(n - 1, max(n - 1 - self.ANCESTORS, 0), -1):
+            yield key[:j]
+
     def _ancestor(self, key: Optional[tuple], root_ends: Sequence[int]):
         """(witness, root-tape nodes of its query) of the nearest of the query's last ANCESTORS
         prefixes that has a witness -- the parent, or past a missed parent the state above it
         (its children are then searched around the last model the path had) -- or (None, 0)."""
-        if not key:
+        p = self._ancestor_key(key)
+        if p is None:
             return None, 0
-        for j in range(len(key) - 1, max(len(key) - 1 - self.ANCESTORS, 0), -1):
-            w = self.witnesses.get(key[:j])
-            if w is not None:
-                return w, (root_ends[j - 1] if j - 1 < len(root_ends) else 0)
-        return None, 0
+        return self.witnesses[p], (root_ends[len(p) - 1] if len(p) - 1 < len(root_ends) else 0)
 
     def _ancestor_key(self, key: Optional[tuple]) -> Optional[tuple]:
         """The key _ancestor's witness is stored under, or None."""
-        if not key:
-            return None
-        for j in range(len(key) - 1, max(len(key) - 1 - self.ANCESTORS, 0), -1):
-            if key[:j] in self.witnesses:
-                return key[:j]
+        for p in self._prefixes(key):
+            if p in self.witnesses:
+                return p
         return None
 
     def _spare_rows(self, key: Optional[tuple], parent, col_index: Dict[str, int], n: int):
@@ -1178,26 +1269,6 @@ class Sieve:
             vals[i] = np.frombuffer(raw, dtype="<u4").reshape(len(names), 8)
         return np.array([col_index[c] for c in names], dtype=np.uint32), vals
 
-    @staticmethod
-    def _composite_spares(columns, group_cols, values: Dict[str, int], ghits, k: int
-                          ) -> List[Dict[str, int]]:
-        """A solved query's spares: spare j (1 <= j < k) takes from every group g its hit
-        j mod n_hits_g (a group solved by one row contributes that row); the query's columns
-        only, a column no conjunct reads at 0 as in the witness.  Spares equal to the witness or
-        to an earlier spare are dropped."""
-        lists = []
-        for g, cols in enumerate(group_cols):
-            lists.append(ghits[g] if ghits[g] else [{columns[c]: values[columns[c]] for c in cols}])
-        base = {c: values[c] for c in columns}
-        out: List[Dict[str, int]] = []
-        for j in range(1, k):
-            row = {c: 0 for c in columns}
-            for rows in lists:
-                row.update(rows[j % len(rows)])
-            if row != base and row not in out:
-                out.append(row)
-        return out
-
     def _parent_kreads(self, b: TapeBuilder, schema: Schema, base_schema: Schema,
                        parent: Dict[str, int]) -> Dict[str, int]:
         """The parent's witness with the keccak read columns of `schema` (the second chance's
@@ -1205,10 +1276,6 @@ class Sieve:
         default lowering gives those applications under it (the stated pair or H(x),
         `base_schema`; one device batch).  The incremental round's parent rows then satisfy
         the parent's keccak conjuncts too."""
-        from copy import deepcopy
-
-        from .lower import Lowering, LoweringUnsupported
-
         need = [c for c in schema.columns.values()
                 if c.kind == "kread" and c.name not in parent]
         if not need:
@@ -1223,7 +1290,7 @@ class Sieve:
         out = dict(parent)
         for c, v in zip(need, vals):
             out[c.name] = v
-        self.stats.extra["parent_kreads"] = self.stats.extra.get("parent_kreads", 0) + 1
+        self.stats.bump("parent_kreads")
         return out
 
     def _attempt(self, b: TapeBuilder, roots: Sequence[int], key: Optional[tuple],
@@ -1231,45 +1298,38 @@ class Sieve:
                  base_schema: Optional[Schema] = None, qno: Optional[int] = None):
         """One lowering of the query and its rounds: (witness or None, schema or REFUTED,
         whether a group left unsolved reads a keccak application).  ``base_schema``: the
-        default lowering's schema, for the second chance's incremental round.  The host stage
-        (_stage), then the rounds (_rounds)."""
+        default lowering's schema, for the second chance's incremental round."""
         staged = self._stage(b, roots, key, keccak_reads,
                              self.stats.queries if qno is None else qno, base_schema)
-        if staged is REFUTED:
+        if staged.refuted:
             return None, REFUTED, False
         return self._rounds(staged, budget, t0)
 
     def _stage(self, b: TapeBuilder, roots: Sequence[int], key: Optional[tuple],
                keccak_reads: bool, qno: int, base_schema: Optional[Schema] = None):
-        """The host stage of one lowering of a query: native build (REFUTED when the query
+        """The host stage of one lowering of a query: native build (a _Refuted when the query
         contradicts itself: no device round), guide harvest and tape compile.  ``qno``: the
         query's number (stats.queries when sequential solve reaches it), which its rounds'
         global_base is made of.  The result owns the guide and the compiled tapes until _rounds
         (or its close()) releases them."""
         st = self.stats
         th = time.perf_counter()
-        self._decide_info = None
-        self._refuted_eligible = False
         host = self._host_native(b, roots, keccak_reads) if self.native_query else None
-        if host is REFUTED:  # no witness exists: no device round (the fallback still runs)
-            self.stats.host_s += time.perf_counter() - th
-            if self._refuted_eligible:
-                self._refuted_unsat.add(qno)
-            return REFUTED
-        dinfo = self._decide_info  # (a query that takes the Python stages is never decided)
-        if host is None:
-            dinfo = None
+        if host is None:  # (a query that takes the Python stages is never decided)
             host = self._host_python(b, roots, keccak_reads)
-        columns, widths, schema, root_nodes, ts, group_cols, defs, root_ends = host
+        if host.refuted:  # no witness exists: no device round (the fallback still runs)
+            self.stats.host_s += time.perf_counter() - th
+            return host
+        columns, widths, ts = host.columns, host.widths, host.ts
         t_t = time.perf_counter()
         pending = None
         try:  # from the compile's start: an error on this side still collects it (ADVICE r5)
             if self.overlap and hasattr(self.ctx, "compile_async"):
                 pending = self.ctx.compile_async(ts)
             col_index = {c: i for i, c in enumerate(columns)}
-            parent, parent_len = self._ancestor(key, root_ends)
+            parent, parent_len = self._ancestor(key, host.root_ends)
             guide = native.harvest_guide(
-                root_nodes, ts.pool.to_array(), widths,
+                host.root_nodes, ts.pool.to_array(), widths,
                 [(col_index[k], v) for k, v in parent.items() if k in col_index] if parent else (),
                 session=self._guide_session(keccak_reads), keep=True)  # kept for the rounds
         except BaseException:
@@ -1300,312 +1360,252 @@ class Sieve:
             guide.close()
             raise
         return _Staged(b, key, keccak_reads, base_schema, qno, host, col_index, parent, parent_len,
-                       guide, ct, t1, dinfo)
+                       guide, ct, t1)
 
-    def _rounds(self, s: "_Staged", budget: float, t0: float, first=None):
+    def _launches(self, s: _Staged) -> Tuple[List[int], bool]:
+        """The rows of a staged query's rounds, and whether the second is the incremental one."""
+        # the incremental round: the parent's witness under the newest root's conjuncts' sets only
+        # (the parent's conjuncts hold there already), instead of the 2^16-row round of the full
+        # guide -- a child whose own conjunct the full guide's rows keep breaking while they break
+        # the parent's (DESIGN §6)
+        inc_ok = bool(s.parent) and s.parent_len > 0 and self.incremental_round
+        launches = [self.first_rows]
+        if self.max_rounds > 1:
+            launches.append(min(self.inc_rows, self.rows) if inc_ok
+                            else (self.max_rounds - 1) * self.rows)
+        if s.keccak_reads and not inc_ok:  # the second chance: one first round
+            launches = launches[:1]
+        if inc_ok and self.round3 and self.max_rounds > 1 and not s.keccak_reads:
+            launches.append((self.max_rounds - 1) * self.rows)  # then the full guide's
+        return launches, inc_ok
+
+    def _incremental_guide(self, s: _Staged):
+        """The incremental round's guide (kept; the caller closes it): harvested from the conjuncts
+        the query adds to its parent's, under the parent's witness.  None when it adds none."""
+        st, host = self.stats, s.host
+        ti = time.perf_counter()
+        inc = newest_tape(host.root_nodes, s.parent_len, self.inc_hops)
+        if inc is None:
+            return None
+        pv = s.parent
+        if s.keccak_reads and s.base_schema is not None and s.base_schema is not REFUTED:
+            pv = self._parent_kreads(s.b, host.schema, s.base_schema, s.parent)
+        guide = native.harvest_guide(
+            inc, host.ts.pool.to_array(), host.widths,
+            [(s.col_index[k], v) for k, v in pv.items() if k in s.col_index],
+            keep=True, parent_eval=self.inc_parent_eval)
+        st.add("guide", time.perf_counter() - ti)
+        st.bump("inc_rounds")
+        self.last_rounds["incremental"] = 1
+        return guide
+
+    def _round(self, run: _Run, rnd: int, n: int, base: int, guide) -> None:
+        """Round `rnd` of a query: `n` rows of `guide` numbered from `base`, over the tapes from
+        the first to the last unsolved group; the groups it answers are taken into `run`."""
+        st, s, solved, n_cols = self.stats, run.s, run.solved, len(run.columns)
+        tb = time.perf_counter()
+        g0 = solved.index(False)
+        g1 = len(solved) - solved[::-1].index(False)
+        hrows, nh, n_sp = None, None, 0
+        if rnd == 0 and run.first is not None:
+            fh, wrows = run.first[0], run.first[1]  # run by solve_many's batched round
+        else:
+            assign = run.assign()
+            # generator, run, and the first witnesses with their rows' columns in one call and one
+            # copy back (mh_query_round)
+            if run.use_hits:
+                # the same round with the K smallest hits of every group listed
+                # (mh_query_round_hits); hit 0 is the witness's row.  The first round's first rows
+                # are the ancestor's witness and spares
+                sp = self._spare_rows(s.key, s.parent, s.col_index, n) if rnd == 0 else None
+                n_sp = len(sp[1]) if sp is not None else 0
+                if rnd == 0:
+                    st.bump("spare_rows", n_sp)
+                    self.last_rounds["spares"] = n_sp
+                    self.last_rounds["spare_hit"] = 0
+                hh, nh, _, hrows = native.query_round_hits(
+                    self.ctx, s.ct, assign, guide, self.seed, base, n, n_cols, self.spares,
+                    spares=sp, tape_first=g0, tape_count=g1 - g0)
+                fh, wrows = hh[:, 0], hrows[:, 0]
+            else:
+                fh, _, wrows = native.query_round(
+                    self.ctx, s.ct, assign, guide, self.seed, base, n, n_cols,
+                    tape_first=g0, tape_count=g1 - g0, mode=native.MODE_FIRST_HIT)
+            st.add("run", time.perf_counter() - tb)
+        st.rounds += 1
+        st.rows += n
+        fresh = []  # the groups this round solves
+        for i, hit in enumerate(fh.tolist()):
+            g = g0 + i
+            if solved[g] or hit == native.NO_HIT:
+                continue
+            run.take(g, wrows[i], hit)
+            fresh.append(hit)
+            if hrows is not None:
+                run.ghits[g] = [_row_values(hrows[i, j], run.columns, run.group_cols[g], {})
+                                for j in range(int(nh[i]))]
+        if n_sp and all(solved) and len(fresh) == len(solved) and max(fresh) < base + n_sp:
+            # every group answered by one of the ancestor's rows
+            st.bump("spare_hits")
+            self.last_rounds["spare_hit"] = 1
+
+    def _rounds(self, s: _Staged, budget: float, t0: float, first=None):
         """The rounds of a staged query: (witness or None, schema, whether a group left unsolved
         reads a keccak application).  ``first`` = (first_hit, witness rows, the buffer they were
         generated into) of its first round when a batched round has run it already: the round
         is then accounted and read as if it had run here."""
-        st = self.stats
-        b, key, keccak_reads, base_schema = s.b, s.key, s.keccak_reads, s.base_schema
-        columns, widths, schema, root_nodes, ts, group_cols, defs, root_ends = s.host
-        col_index, parent, parent_len = s.col_index, s.parent, s.parent_len
-        guide, ct, t1 = s.guide, s.ct, s.t1
+        st, schema = self.stats, s.host.schema
         t_c = time.perf_counter()
-        round_guide = guide  # the incremental round's own guide replaces it (closed below)
+        run = _Run(self, s, first, budget, t0)
         inc_guide = None
-        ft, nt = getattr(ct, "timing", (0.0, 0.0))
+        ft, nt = getattr(s.ct, "timing", (0.0, 0.0))
         st.add("compile_flatten", ft)
         st.add("compile_native", nt)
         try:
-            # (after a batched first round the sieve's own buffer is made when a later round or
-            # the repair step needs it)
-            assign = self._buffer(len(columns)) if first is None else None
-            values: Dict[str, int] = {}
-            solved = [False] * len(group_cols)
-            # spare witnesses: a sequential query's guided rounds list K hits per group
-            use_hits = self.spares > 0 and first is None
-            ghits: List[Optional[List[Dict[str, int]]]] = [None] * len(group_cols)
-            n_sp = 0
-            first_index = None
+            launches, inc_ok = self._launches(s)
+            self.last_rounds = {"groups": len(run.solved), "r1_solved": 0, "rounds": 0}
+            round_guide = s.guide  # the incremental round's own guide replaces it (closed below)
+            offset = (1 << 23) if s.keccak_reads else 0
             last_n = 0
-            offset = (1 << 23) if keccak_reads else 0
-            # the incremental round: the parent's witness under the newest root's conjuncts'
-            # sets only (the parent's conjuncts hold there already), instead of the 2^16-row
-            # round of the full guide -- a child whose own conjunct the full guide's rows keep
-            # breaking while they break the parent's (DESIGN §6)
-            inc_ok = bool(parent) and parent_len > 0 and self.incremental_round
-            launches = [self.first_rows]
-            if self.max_rounds > 1:
-                launches.append(min(self.inc_rows, self.rows) if inc_ok
-                                else (self.max_rounds - 1) * self.rows)
-            self.last_rounds = {"groups": len(group_cols), "r1_solved": 0, "rounds": 0}
-            if keccak_reads and not inc_ok:  # the second chance: one first round
-                launches = launches[:1]
-            if inc_ok and self.round3 and self.max_rounds > 1 and not keccak_reads:
-                launches.append((self.max_rounds - 1) * self.rows)  # then the full guide's
             for rnd, n in enumerate(launches):
                 if rnd == 2:
-                    round_guide = guide
+                    round_guide = s.guide
                 if rnd == 1:
-                    k = sum(solved)
+                    k = sum(run.solved)
                     self.last_rounds["r1_solved"] = k
                     if self.second_round == "never" or (self.second_round == "progress"
                                                         and k == 0):
-                        self.stats.extra["round2_skipped"] = \
-                            self.stats.extra.get("round2_skipped", 0) + 1
+                        st.bump("round2_skipped")
                         break
                     if inc_ok:
-                        ti = time.perf_counter()
-                        inc = newest_tape(root_nodes, parent_len, self.inc_hops)
-                        if inc is None:
+                        round_guide = inc_guide = self._incremental_guide(s)
+                        if inc_guide is None:
                             break
-                        pv = parent
-                        if keccak_reads and base_schema is not None \
-                                and base_schema is not REFUTED:
-                            pv = self._parent_kreads(b, schema, base_schema, parent)
-                        round_guide = inc_guide = native.harvest_guide(
-                            inc, ts.pool.to_array(), widths,
-                            [(col_index[k], v) for k, v in pv.items() if k in col_index],
-                            keep=True, parent_eval=self.inc_parent_eval)
-                        st.add("guide", time.perf_counter() - ti)
-                        st.extra["inc_rounds"] = st.extra.get("inc_rounds", 0) + 1
-                        self.last_rounds["incremental"] = 1
                 self.last_rounds["rounds"] = rnd + 1
                 base = (s.qno << 24) + offset
                 offset += n
                 last_n = n
-                tb = time.perf_counter()
-                # a later round runs only the tapes from the first to the last unsolved group
-                g0 = solved.index(False)
-                g1 = len(solved) - solved[::-1].index(False)
-                hrows = nh = None
-                if rnd == 0 and first is not None:
-                    fh, wrows = first[0], first[1]  # run by solve_many's batched round
-                else:
-                    if assign is None:
-                        assign = self._buffer(len(columns))
-                    # generator, run, and the first witnesses with their rows' columns in one call
-                    # and one copy back (mh_query_round)
-                    if use_hits:
-                        # the same round with the K smallest hits of every group listed
-                        # (mh_query_round_hits); hit 0 is the witness's row as below.  The first
-                        # round's first rows are the ancestor's witness and spares
-                        sp = self._spare_rows(key, parent, col_index, n) if rnd == 0 else None
-                        n_sp = len(sp[1]) if sp is not None else 0
-                        if rnd == 0:
-                            st.extra["spare_rows"] = st.extra.get("spare_rows", 0) + n_sp
-                            self.last_rounds["spares"] = n_sp
-                            self.last_rounds["spare_hit"] = 0
-                        hh, nh, _, hrows = native.query_round_hits(
-                            self.ctx, ct, assign, round_guide, self.seed, base, n, len(columns),
-                            self.spares, spares=sp, tape_first=g0, tape_count=g1 - g0)
-                        fh, wrows = hh[:, 0], hrows[:, 0]
-                    else:
-                        fh, _, wrows = native.query_round(
-                            self.ctx, ct, assign, round_guide, self.seed, base, n, len(columns),
-                            tape_first=g0, tape_count=g1 - g0, mode=native.MODE_FIRST_HIT)
-                    tr = time.perf_counter()
-                    st.add("run", tr - tb)
-                self.stats.rounds += 1
-                self.stats.rows += n
-                fresh = []  # the groups this round solves
-                for i, hit in enumerate(fh.tolist()):
-                    g = g0 + i
-                    if solved[g] or hit == native.NO_HIT:
-                        continue
-                    # the row's columns as 32 little-endian bytes each
-                    raw = np.ascontiguousarray(wrows[i], dtype="<u4").tobytes()
-                    for c in group_cols[g]:
-                        values[columns[c]] = int.from_bytes(raw[32 * c:32 * c + 32], "little")
-                    solved[g] = True
-                    fresh.append(hit)
-                    first_index = hit if first_index is None else min(first_index, hit)
-                    if use_hits and hrows is not None:
-                        ghits[g] = []
-                        for j in range(int(nh[i])):
-                            raw = np.ascontiguousarray(hrows[i, j], dtype="<u4").tobytes()
-                            ghits[g].append({
-                                columns[c]: int.from_bytes(raw[32 * c:32 * c + 32], "little")
-                                for c in group_cols[g]})
-                if (use_hits and rnd == 0 and n_sp and all(solved)
-                        and len(fresh) == len(solved) and max(fresh) < base + n_sp):
-                    # every group answered by one of the ancestor's rows
-                    st.extra["spare_hits"] = st.extra.get("spare_hits", 0) + 1
-                    self.last_rounds["spare_hit"] = 1
-                if all(solved):
-                    for c in columns:  # columns no conjunct reads: any value is a model
-                        values.setdefault(c, 0)
-                    if defs:  # defined symbols take their terms' values under the row
-                        td = time.perf_counter()
-                        got = self.eval_definitions(b, defs, columns, values)
-                        for (c, _), v in zip(defs, got):
-                            values[c] = v
-                        st.add("definitions", time.perf_counter() - td)
+                self._round(run, rnd, n, base, round_guide)
+                if all(run.solved):
+                    w = run.complete(rnd + 1)
                     if rnd and inc_ok:
-                        st.extra["inc_hits"] = st.extra.get("inc_hits", 0) + 1
-                    w = Witness(schema, values, first_index, rnd + 1)
-                    if use_hits:
-                        w.spares = self._composite_spares(columns, group_cols, values, ghits,
-                                                          self.spares)
+                        st.bump("inc_hits")
                     return w, schema, False
-                if time.perf_counter() - t0 > budget:
+                if run.spent():
                     break
-            if (self.repair_rounds > 0 and last_n and not all(solved)
-                    and time.perf_counter() - t0 <= budget):
-                if assign is None:
+            if self.repair_rounds > 0 and last_n and not all(run.solved) and not run.spent():
+                if run.buffer is None:
                     # repair straight after a batched first round: its rows regenerated into the
                     # buffer repair reads (and writes children into), the one sequential solve
                     # leaves them in -- one deterministic launch on a rare path
-                    assign = self._buffer(len(columns))
-                    assign.generate_guided(self.seed, guide.arrays(), global_base=s.qno << 24,
-                                           first=0, count=last_n)
-                    st.extra["repair_regenerated"] = st.extra.get("repair_regenerated", 0) + 1
-                base = (s.qno << 24) + offset
-                hit = self._repair(root_nodes, ts, ct, guide, assign, last_n, columns, group_cols,
-                                   solved, values, base, budget, t0)
-                if hit is not None:
-                    first_index = hit if first_index is None else min(first_index, hit)
-                if all(solved):
-                    for c in columns:
-                        values.setdefault(c, 0)
-                    if defs:
-                        td = time.perf_counter()
-                        got = self.eval_definitions(b, defs, columns, values)
-                        for (c, _), v in zip(defs, got):
-                            values[c] = v
-                        st.add("definitions", time.perf_counter() - td)
-                    w = Witness(schema, values, first_index, self.last_rounds["rounds"],
-                                repaired=True)
-                    if use_hits:
-                        w.spares = self._composite_spares(columns, group_cols, values, ghits,
-                                                          self.spares)
-                    return w, schema, False
-            if self.decide_rows > 0 and s.decide is not None and not all(solved):
-                if assign is None:
-                    assign = self._buffer(len(columns))
-                unsat, hit = self._decide(s.decide, ts, ct, assign, columns, widths, group_cols,
-                                          solved, values, budget, t0)
+                    run.assign().generate_guided(self.seed, s.guide.arrays(),
+                                                 global_base=s.qno << 24, first=0, count=last_n)
+                    st.bump("repair_regenerated")
+                self._repair(run, last_n, (s.qno << 24) + offset)
+                if all(run.solved):
+                    return run.complete(self.last_rounds["rounds"], repaired=True), schema, False
+            if self.decide_rows > 0 and s.host.decide is not None and not all(run.solved):
+                unsat, _ = self._decide(run)
                 if unsat:  # an eligible group has no row: no witness, and no second chance
                     self.last_unsat = True
-                    st.extra["decided_unsat"] = st.extra.get("decided_unsat", 0) + 1
+                    st.bump("decided_unsat")
                     return None, schema, False
-                if hit is not None:
-                    first_index = hit if first_index is None else min(first_index, hit)
-                if all(solved):
-                    for c in columns:
-                        values.setdefault(c, 0)
-                    if defs:
-                        td = time.perf_counter()
-                        got = self.eval_definitions(b, defs, columns, values)
-                        for (c, _), v in zip(defs, got):
-                            values[c] = v
-                        st.add("definitions", time.perf_counter() - td)
-                    w = Witness(schema, values, first_index, self.last_rounds.get("rounds", 0))
-                    if use_hits:
-                        w.spares = self._composite_spares(columns, group_cols, values, ghits,
-                                                          self.spares)
-                    return w, schema, False
-            kec = any(not solved[g] and _reads_keccak(ts.tapes[g].nodes)
-                      for g in range(len(solved)))
+                if all(run.solved):
+                    return run.complete(self.last_rounds.get("rounds", 0)), schema, False
+            kec = any(not run.solved[g] and _reads_keccak(s.host.ts.tapes[g].nodes)
+                      for g in range(len(run.solved)))
             return None, schema, kec
         finally:
-            ct.close()
-            guide.close()
+            s.ct.close()
+            s.guide.close()
             if inc_guide is not None:
                 inc_guide.close()
             # (a batched query's stage ended before the other queries' stages and the batch)
-            self.stats.device_s += time.perf_counter() - (t1 if first is None else t_c)
+            self.stats.device_s += time.perf_counter() - (s.t1 if first is None else t_c)
 
-    def _decide(self, info, ts, ct, assign, columns, widths, group_cols, solved, values, budget,
-                t0):
+    def _decide(self, run: _Run):
         """The decision step (DESIGN §6 "Decision by enumeration"), after the rounds and repair:
         every group still unsolved that is eligible (decide.eligible: UNSAT of the lowered group
         implies UNSAT of the caller's constraints) and whose domains' cross product has at most
         decide_rows rows is enumerated in order, in windows of the sieve's buffer
-        (mh_query_enumerate, FIRST_HIT), up to the first window with a hit.  A hit fills
-        `values` / `solved` as a round's does.  Returns (whether some group was found empty --
+        (mh_query_enumerate, FIRST_HIT), up to the first window with a hit.  A hit is taken into
+        `run` as a round's is.  Returns (whether some group was found empty --
         no rows at all, or enumerated to the end without a hit -- which makes the query UNSAT,
         the smallest hit index or None).  A group whose enumeration the budget cuts short stays
         undecided, never empty."""
-        st = self.stats
-        ex = st.extra
+        st, host, solved, group_cols = self.stats, run.s.host, run.solved, run.group_cols
+        ts, assign = host.ts, run.assign()
         first_hit = None
         consts = ts.pool.to_array()
         for g in range(len(solved)):
             if solved[g]:  # (a ground group's product is the one empty row: its tape decides)
                 continue
             nodes = ts.tapes[g].nodes
-            if not decide.eligible(*info, group_cols[g], nodes):
-                ex["decide_ineligible"] = ex.get("decide_ineligible", 0) + 1
+            if not decide.eligible(*host.decide, group_cols[g], nodes):
+                st.bump("decide_ineligible")
                 continue
             td = time.perf_counter()
-            dom = native.domains_build(nodes, consts, widths, group_cols[g])
+            dom = native.domains_build(nodes, consts, host.widths, group_cols[g])
             try:
                 if dom.rows > self.decide_rows:
-                    ex["decide_too_large"] = ex.get("decide_too_large", 0) + 1
+                    st.bump("decide_too_large")
                     continue
                 window = assign.capacity
                 base, hit, row = 0, None, None
                 while base < dom.rows:
-                    if time.perf_counter() - t0 > budget:
+                    if run.spent():
                         break
                     n = min(window, dom.rows - base)
-                    fh, _, wrows = native.query_enumerate(self.ctx, ct, assign, dom, base, n,
-                                                          len(columns), tape=g,
+                    fh, _, wrows = native.query_enumerate(self.ctx, run.s.ct, assign, dom, base, n,
+                                                          len(run.columns), tape=g,
                                                           mode=native.MODE_FIRST_HIT)
-                    ex["decide_rows"] = ex.get("decide_rows", 0) + n
+                    st.bump("decide_rows", n)
                     st.rows += n
                     base += n
                     if int(fh[0]) != native.NO_HIT:
                         hit, row = int(fh[0]), wrows[0]
                         break
                 if hit is not None:
-                    raw = np.ascontiguousarray(row, dtype="<u4").tobytes()
-                    for c in group_cols[g]:
-                        values[columns[c]] = int.from_bytes(raw[32 * c:32 * c + 32], "little")
-                    solved[g] = True
+                    run.take(g, row, hit)
                     first_hit = hit if first_hit is None else min(first_hit, hit)
-                    ex["decided_sat"] = ex.get("decided_sat", 0) + 1
+                    st.bump("decided_sat")
                 elif base >= dom.rows:  # the whole product (or an empty one) holds no model
                     return True, first_hit
                 else:
-                    ex["decide_budget"] = ex.get("decide_budget", 0) + 1
+                    st.bump("decide_budget")
             finally:
                 dom.close()
                 st.add("decide", time.perf_counter() - td)
         return False, first_hit
 
-    def _repair(self, root_nodes, ts, ct, guide, assign, n_rows, columns, group_cols, solved,
-                values, base, budget, t0):
+    def _repair(self, run: _Run, n_rows: int, base: int):
         """The repair step, after an attempt's ordinary rounds left groups unsolved:
-        per unsolved group, the rows the last round left in `assign` are scored by the group's
-        conjuncts they fail (mh_repair_score over the conjunct plan's tapes), the best K kept
+        per unsolved group, the `n_rows` rows the last round left in the buffer are scored by the
+        group's conjuncts they fail (mh_repair_score over the conjunct plan's tapes), the best K kept
         (mh_repair_select) and `per` children made of each with ONE failing conjunct's columns
         regenerated from that conjunct's own sets (mh_repair_mutate); the group's tape decides
         over the children as in an ordinary round, and the children are scored for the next
-        iteration.  Fills `values` / `solved` for the groups it answers; returns the smallest
-        hit index or None."""
-        st = self.stats
-        ex = st.extra
+        iteration (children numbered from `base`).  The groups it answers are taken into `run`;
+        returns the smallest hit index or None."""
+        st, s, solved, group_cols = self.stats, run.s, run.solved, run.group_cols
+        columns, ts, ct, guide, assign = run.columns, s.host.ts, s.ct, s.guide, run.assign()
         K, per = self.repair_elites, self.repair_children
         n_rows = min(n_rows, self.repair_score_rows)
         lr = self.last_rounds
         lr["repair"] = 0
-        first_hit = None
-        set_leaf = None
+        first_hit = set_leaf = None
         for g in range(len(solved)):
             if solved[g] or not group_cols[g]:  # (a ground group has no column to repair)
                 continue
-            if time.perf_counter() - t0 > budget:
+            if run.spent():
                 break
             tr = time.perf_counter()
             try:
-                plan = native.ConjunctPlan(root_nodes, group_cols[g] if len(group_cols) > 1 else (),
+                plan = native.ConjunctPlan(s.host.root_nodes,
+                                           group_cols[g] if len(group_cols) > 1 else (),
                                            self.repair_max_conjuncts)
             except native.Unsupported:  # one conjunct, or too many: no repair for this group
-                ex["repair_skipped"] = ex.get("repair_skipped", 0) + 1
+                st.bump("repair_skipped")
                 continue
             cts = TapeSet(columns)
             cts.pool = ts.pool
@@ -1614,10 +1614,10 @@ class Sieve:
             try:
                 cct = self.compile(cts)
             except native.Unsupported:
-                ex["repair_skipped"] = ex.get("repair_skipped", 0) + 1
+                st.bump("repair_skipped")
                 continue
             try:
-                ex["repair_tries"] = ex.get("repair_tries", 0) + 1
+                st.bump("repair_tries")
                 if set_leaf is None:
                     set_leaf = guide.set_conjuncts()
                 tags = plan.set_ordinals(set_leaf)
@@ -1636,14 +1636,14 @@ class Sieve:
                 native.repair_score(rep, cct, src, row_count=n_rows)
                 best_seen, stalled = None, 0
                 for it in range(self.repair_rounds):
-                    if time.perf_counter() - t0 > budget:
+                    if run.spent():
                         break
                     el = native.repair_select(rep, K, self.seed + it)
                     best = int(el[0]["fail_count"])
                     if it == 0 and best > self.repair_max_fail:
-                        ex["repair_far"] = ex.get("repair_far", 0) + 1
+                        st.bump("repair_far")
                         break
-                    row = None
+                    hit = native.NO_HIT
                     if best == 0:
                         # every conjunct of the group holds on the row: confirmed by the group's own
                         # tape, the authority of an ordinary round
@@ -1652,17 +1652,15 @@ class Sieve:
                                                        tape_count=1, row_first=r0, row_count=1,
                                                        index_base=base - r0,
                                                        mode=native.MODE_FIRST_HIT)
-                        if int(fh[0]) != native.NO_HIT:
-                            row = wrows[0]
-                            hit = int(fh[0])
-                    if row is None:
+                        hit = int(fh[0])
+                    if hit == native.NO_HIT:
                         if best_seen is not None and best >= best_seen:
                             stalled += 1
                             if stalled >= self.repair_stall:
                                 break
                         else:
                             best_seen, stalled = best, 0
-                        ex["repair_iters"] = ex.get("repair_iters", 0) + 1
+                        st.bump("repair_iters")
                         lr["repair"] += 1
                         n_ch = len(el) * per
                         native.repair_mutate(rep, src, dst, guide, tags, plan.col_off,
@@ -1672,19 +1670,14 @@ class Sieve:
                                                        index_base=base, mode=native.MODE_FIRST_HIT)
                         st.rows += n_ch
                         base += n_ch
-                        if int(fh[0]) != native.NO_HIT:
-                            row = wrows[0]
-                            hit = int(fh[0])
-                        else:
+                        hit = int(fh[0])
+                        if hit == native.NO_HIT:
                             native.repair_score(rep, cct, dst, row_count=n_ch)
                             src, dst = dst, src
                             continue
-                    raw = np.ascontiguousarray(row, dtype="<u4").tobytes()
-                    for c in group_cols[g]:
-                        values[columns[c]] = int.from_bytes(raw[32 * c:32 * c + 32], "little")
-                    solved[g] = True
+                    run.take(g, wrows[0], hit)
                     first_hit = hit if first_hit is None else min(first_hit, hit)
-                    ex["repair_hits"] = ex.get("repair_hits", 0) + 1
+                    st.bump("repair_hits")
                     break
             finally:
                 cct.close()
@@ -1727,8 +1720,6 @@ def newest_tape(nodes: np.ndarray, parent_len: int, hops: int = 0) -> Optional[n
                 leaves.append(y)
     if hops:
         leaves = _column_neighbours(nodes, parent_len - 1, leaves) + leaves
-    from .tape import ARITY
-
     ar = {int(o): ARITY[o] for o in Op}
     remap: Dict[int, int] = {}
     out: List[np.void] = []
@@ -1761,8 +1752,6 @@ def newest_tape(nodes: np.ndarray, parent_len: int, hops: int = 0) -> Optional[n
 def _column_neighbours(nodes: np.ndarray, parent_root: int, leaves: List[int]) -> List[int]:
     """The AND leaves under `parent_root` that read a column one of `leaves` reads."""
     op, a, bb, cc, i0 = nodes["op"], nodes["a"], nodes["b"], nodes["c"], nodes["imm0"]
-    from .tape import ARITY
-
     ar = {int(o): ARITY[o] for o in Op}
     VAR, AND = int(Op.VAR), int(Op.AND)
 

@@ -147,7 +147,7 @@ def first_round(k, reps, warmup):
     out = []
     try:
         st = s._stage(ctx.b, [c.node for c in cs], None, False, 1)
-        columns = st.host[0]
+        columns = st.host.columns
         assign = s._buffer(len(columns))
         n = s.first_rows
         calls = {

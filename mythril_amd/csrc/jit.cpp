@@ -144,6 +144,7 @@ private:
     int cold_ = 0;
     bool calls_div_ = false;
     bool calls_divw_ = false;  // some site calls a width-specialised variant (op_div)
+    bool calls_dive_ = false;  // some site calls through the level-6 entry head (op_div)
     bool uses_lds_ = false;
     bool calls_kec_ = false;
     int cur_op_ = -1;  // SSA op being emitted (diagnostic attribution)
@@ -152,6 +153,7 @@ public:
     static uint64_t op_valu[256], op_wide[256], op_count[256];
     int div_ = 0;  // inline division fast paths (op_div): the MH_JIT_DIV level, 0 = off
     bool divw_ = false;  // width-specialised division variants (MH_JIT_STAGE >= 5, MH_JIT_DIV > 0)
+    int dive_ = 0;  // MH_JIT_STAGE >= 6, MH_JIT_DIV > 0: bit 0 raw srem entry, bit 1 run-time width dispatch
 private:
 
     // ---- emission
@@ -1521,7 +1523,24 @@ void Emitter::op_div(int d, int a, int b, int cidx, uint32_t kind, int cur) {
         emit(M_LABEL, {LBL(l_cold)});
         ++cold_;
     }
-    if (kind < 2) {
+    // Raw srem entry: srem of full-width operands of unknown sign loads
+    // both operands as they are, with their sign masks, and enters the subroutine at L_SRAW, which
+    // forms |x|, |y| itself only in a wave with an undecided lane.  The sign masks first: the
+    // copies stay next to the call (coalesce_div_moves), and an operand may sit in R.
+    const bool raw = (dive_ & 1) && path == 0 && kind == 3 && nx == 8 && ny == 8 && A.l[7].is_r() &&
+                     B.l[7].is_r();
+    if (raw) {
+        // the lanes whose result is read (valid, and true in the Bool tested last), as the inline
+        // paths take them (div_undecided): only they have to be decided
+        emit(M_S_MOV_B64, {S(S_DIV_TM, 2), S(S_VALID, 2)});
+        const int lv = live_vreg_;
+        if (check_ && lv >= 0 && vals_[lv].defined && vals_[lv].is_bool && vals_[lv].bconst < 0 &&
+            last_[lv] > cur)
+            emit(M_S_AND_B64, {S(S_DIV_TM, 2), S(S_DIV_TM, 2), P(vals_[lv].pair)});
+        emit(M_V_ASHRREV, {V(R_SY), IMM(31), V(B.l[7].v)});
+        emit(M_V_ASHRREV, {V(R_SX), IMM(31), V(A.l[7].v)});
+    }
+    if (kind < 2 || raw) {
         for (int k = 0; k < 8; ++k) emit(M_V_MOV, {V(R_DY + k), src(B.l[k])});
         for (int k = 0; k < 8; ++k) emit(M_V_MOV, {V(R_DR + k), src(A.l[k])});
     } else {
@@ -1604,9 +1623,16 @@ void Emitter::op_div(int d, int a, int b, int cidx, uint32_t kind, int cur) {
             emit(M_S_MOV_B32, {S(S_DIV_F64K), IMM((uint32_t)rb)});
             emit(M_S_MOV_B32, {S(S_DIV_F64K + 1), IMM((uint32_t)(rb >> 32))});
         }
+    } else if (raw) {
+        // e = 128 + the highest demanded limb of the result (the hot side stops there)
+        emit(M_S_MOV_B32, {S(S_DIV_KIND), IMM(kind | (128u + (uint32_t)std::max(top_bit(dm), 0)) << 3)});
+        // whether the fallback into the legacy code may use the width dispatch
+        emit(M_S_MOV_B32, {S(S_DIV_FLAG6), IMM((dive_ & 2) ? 1u : 0u)});
     } else {
-        emit(M_S_MOV_B32, {S(S_DIV_KIND), IMM(kind)});
+        // level 6: bit 11 lets the legacy code hand a uniformly short divisor to its variant
+        emit(M_S_MOV_B32, {S(S_DIV_KIND), IMM((dive_ & 2) ? kind | 2048u : kind)});
     }
+    if (dive_) calls_dive_ = true;
     emit(M_CALL_DIV, {IMM((uint32_t)code_.size())});
     if (path) {
         --cold_;
@@ -2645,6 +2671,7 @@ TapeCode Emitter::run() {
     tc.max_vgpr = vhigh_;
     tc.calls_div = calls_div_;
     tc.calls_divw = calls_divw_;
+    tc.calls_dive = calls_dive_;
     tc.uses_lds = uses_lds_;
     tc.calls_kec = calls_kec_;
     tc.n_valu = n_valu_;
@@ -2816,6 +2843,28 @@ std::vector<MI> div_routine() {
                       L_WOK = 152 /* + ny */, L_WZQ = 160 /* + 2 (8 c + ny) */,
                       L_WSTEP = 256 /* + 16 ny + j */, L_WNONEG = 384, L_WNOGE = 512,
                       L_WTREE = 640 };
+    // ---- level-6 entries (round 11): the head.  Labels 200..203 mark what build_module prints
+    // only into a module with a level-6 call site: [L_EHEAD, L_WHEAD), [L_BSEC, L_BEND) and
+    // [L_ESEC, end); the labels below 128 inside them are the ones the emulator counts.
+    //   S_DIV_KIND >= 2048: a legacy site (kind | 2048); FLAG6 = 1 lets the legacy code hand a
+    // uniformly short divisor to its variant (L_BSEC).  1024..2047: the raw srem entry (L_SRAW),
+    // whose site writes FLAG6 itself.
+    // Below 1024: a variant site, or a site of a lower level in the emulator's one routine.
+    enum : uint32_t { L_SRAW = 113, L_SCOLD, L_BNO, L_BGO /* + k, 1..6 */, L_EOLD = 123, L_SFULL,
+                      L_EHEAD = 200, L_ESEC, L_BSEC, L_BEND };
+    const Opnd FLAG6 = S(S_DIV_FLAG6);
+    L(L_EHEAD);
+    E(M_S_CMP_LT_U32, {KIND, IMM(1024)});
+    E(M_S_CBRANCH_SCC1, {LBL(L_EOLD)});
+    E(M_S_CMP_LT_U32, {KIND, IMM(2048)});
+    E(M_S_CBRANCH_SCC1, {LBL(L_SRAW)});
+    // kind = S_DIV_KIND & 7: the instruction list has no 32-bit scalar AND, so the 64-bit one
+    // over s[80:81]; its upper half is FLAG6, written next
+    E(M_S_AND_B64, {S(S_DIV_KIND, 2), S(S_DIV_KIND, 2), IMM(7)});
+    E(M_S_MOV_B32, {FLAG6, IMM(1)});
+    E(M_S_BRANCH, {LBL(L_UNS)});
+    L(L_EOLD);
+    E(M_S_MOV_B32, {FLAG6, IMM(0)});
     L(L_WHEAD);
     E(M_S_CMP_LT_U32, {KIND, IMM(64)});
     E(M_S_CBRANCH_SCC1, {LBL(L_UNS)});
@@ -2916,6 +2965,50 @@ std::vector<MI> div_routine() {
     E(M_V_CMP_NE, {VCC(), IMM(0), Yr(7)});
     E(M_S_ANDN2_B64, {TM, MSK, VCC()});
     E(M_S_CBRANCH_SCC0, {LBL(L_F32)});
+    // ---- run-time width dispatch (round 11, level-6 sites: FLAG6).  Some lane that needs a digit
+    // has a divisor short only at run time.  When limb k >= 1 of y is nonzero in every lane and
+    // the limbs above it are zero in every lane, the wave is what variant ny = k + 1 serves (its
+    // guard holds by construction, no lane has y = 0), and its digit steps convert ny + 1 limbs
+    // where the steps below convert all eight.  The start digit comes from x the same way:
+    // with limbs nx.. of x zero in every lane, j0 = max(nx - ny, 0) keeps the variants'
+    // invariant, x < 2^(32 nx) <= y 2^(32 (j0 + 1)), and leading zero digits cost nothing.  The
+    // quotient registers are zeroed already (L_ZQ); the variants restore S_DIV_KIND from KEEP.
+    // VCC holds y7 != 0 per lane on entry.
+    L(L_BSEC);
+    E(M_S_CMP_EQ_U32, {FLAG6, IMM(1)});
+    E(M_S_CBRANCH_SCC0, {LBL(L_BNO)});
+    E(M_S_CMP_LG_U64, {VCC(), IMM(0)});
+    E(M_S_CBRANCH_SCC1, {LBL(L_BNO)});
+    for (int k = 6; k >= 1; --k) {
+        E(M_V_CMP_NE, {VCC(), IMM(0), Yr(k)});
+        E(M_S_CMP_EQ_U64, {VCC(), IMM(0xFFFFFFFFu)});
+        E(M_S_CBRANCH_SCC1, {LBL(L_BGO + (uint32_t)k)});
+        E(M_S_CMP_LG_U64, {VCC(), IMM(0)});
+        E(M_S_CBRANCH_SCC1, {LBL(L_BNO)});
+    }
+    E(M_S_BRANCH, {LBL(L_BNO)});
+    for (int k = 6; k >= 1; --k) {
+        const int ny = k + 1, jmax = 8 - ny, wl = std::min(ny, 3);
+        L(L_BGO + (uint32_t)k);
+        E(M_S_MOV_B32, {S(S_DIV_DUMMY), KIND});
+        E(M_S_MOV_B32, {K64LO, IMM(0)});
+        E(M_S_MOV_B32, {K64HI, IMM(0x41f00000u)});  // 2^32
+        E(M_V_CVT_F64_U32, {FY, Yr(ny - 1)});
+        for (int i = ny - 2; i >= ny - wl; --i) {
+            E(M_V_CVT_F64_U32, {FT, Yr(i)});
+            E(M_V_FMA_F64, {FY, FY, K64, FT});
+        }
+        recip();
+        E(M_S_MOV_B64, {YNZ, IMM(0xFFFFFFFFu)});
+        for (int j = jmax; j >= 1; --j) {  // x's limb j + ny - 1 nonzero in some lane: digit j
+            E(M_V_CMP_NE, {VCC(), IMM(0), Rr(j + ny - 1)});
+            E(M_S_CMP_LG_U64, {VCC(), IMM(0)});
+            E(M_S_CBRANCH_SCC1, {LBL(L_WSTEP + 16 * (uint32_t)ny + (uint32_t)j)});
+        }
+        E(M_S_BRANCH, {LBL(L_WSTEP + 16 * (uint32_t)ny)});
+    }
+    L(L_BNO);
+    L(L_BEND);
     to_f64(FY, Yl);
     recip();
     to_f64(FR, Rl);
@@ -3371,6 +3464,89 @@ std::vector<MI> div_routine() {
         }
         leave(L_DONE);
     }
+    // ---- raw srem entry (round 11) ------------------------------------------------
+    // x and y arrive as they are, full width, with their sign masks in SX, SY, and
+    // S_DIV_KIND = 3 | (128 + top) << 3, top = the highest demanded limb of the result.
+    // With c = floor(|x| / |y|), bvsrem is r = x - s c y mod 2^256, s = -1 where the signs differ;
+    // c y mod 2^256 is the same over y's raw limbs, so with m = SX ^ SY and P = c y,
+    // r = x - ((P ^ m) - m): one borrow chain over P_k ^ m with the borrow set on entry where
+    // m != 0.  c is div_small_quotient's estimate over the one's complements x ^ sx, y ^ sy under
+    // its decided test (its proof: a decided lane has c exact), over the lanes whose result is
+    // read, which the site passes in S_DIV_TM (valid, and true in the Bool tested last).  Every
+    // such lane decided: no |x|, no |y|, no add-back, no sign fix; the other lanes' results are
+    // never read.  Otherwise |x|, |y| are formed in place and the legacy code runs.
+    L(L_ESEC);
+    L(L_SRAW);
+    {
+        const Opnd K32 = K64LO, KT = K64HI, ONE = S(S_DIV_YNZ);
+        // a short divisor first (the usual reason for a wave to be undecided: such operands are
+        // short by construction, row after row): it leaves after two VALU instead of the estimate
+        E(M_V_XOR, {V(R_MAD), Yr(7), SY});
+        E(M_V_CMP_NE, {VCC(), IMM(0), V(R_MAD)});  // top limb of y ^ sy nonzero
+        E(M_S_ANDN2_B64, {DUMMY, TM, VCC()});
+        E(M_S_CBRANCH_SCC1, {LBL(L_SCOLD)});
+        E(M_V_XOR, {V(R_MAD + 1), Yr(6), SY});
+        E(M_V_XOR, {V(R_CARRY), Rr(7), SX});
+        E(M_V_XOR, {V(R_CARRY + 1), Rr(6), SX});
+        E(M_S_MOV_B32, {K32, IMM(0x4f800000u)});  // 2^32
+        E(M_V_CVT_F32_U32, {V(R_FT), V(R_CARRY)});
+        E(M_V_CVT_F32_U32, {V(R_FT + 1), V(R_CARRY + 1)});
+        E(M_V_FMA_F32, {V(R_FR), V(R_FT), K32, V(R_FT + 1)});
+        E(M_V_CVT_F32_U32, {V(R_FT), V(R_MAD)});
+        E(M_V_CVT_F32_U32, {V(R_FT + 1), V(R_MAD + 1)});
+        E(M_V_FMA_F32, {V(R_FY), V(R_FT), K32, V(R_FT + 1)});
+        E(M_V_RCP_F32, {V(R_FY), V(R_FY)});
+        E(M_S_NOP, {IMM(1)});  // trans result -> non-trans VALU use needs a wait state
+        E(M_V_MUL_F32, {V(R_FC), V(R_FR), V(R_FY)});
+        E(M_V_CMP_GT_F32, {VCC(), IMM(0x44800000u), V(R_FC)});  // e < 2^10 (false for NaN, inf)
+        E(M_S_MOV_B64, {MSK, VCC()});
+        E(M_V_FRACT_F32, {V(R_FT), V(R_FC)});
+        E(M_S_MOV_B32, {KT, IMM(0x35800000u)});  // 2^-20
+        E(M_V_FMA_F32, {T1, V(R_FC), KT, KT});  // thr
+        E(M_V_CMP_GT_F32, {VCC(), T1, V(R_FT)});  // the fraction below thr ...
+        E(M_S_MOV_B64, {DUMMY, VCC()});
+        E(M_V_CMP_LE_F32, {VCC(), IMM(0x3f800000u), V(R_FC)});  // ... of an estimate >= 1
+        E(M_S_AND_B64, {DUMMY, DUMMY, VCC()});
+        E(M_S_ANDN2_B64, {MSK, MSK, DUMMY});
+        E(M_S_MOV_B32, {ONE, IMM(0x3f800000u)});
+        E(M_V_FMA_F32, {T1, T1, ONE, V(R_FT)});  // fraction + thr
+        E(M_V_CMP_LE_F32, {VCC(), IMM(0x3f800000u), T1});  // >= 1
+        E(M_S_ANDN2_B64, {MSK, MSK, VCC()});
+        E(M_S_ANDN2_B64, {DUMMY, TM, MSK});  // SCC = some lane whose result is read is undecided
+        E(M_S_CBRANCH_SCC1, {LBL(L_SCOLD)});
+        E(M_V_CVT_U32_F32, {C, V(R_FC)});
+        E(M_V_XOR, {T1, SX, SY});
+        E(M_V_CMP_NE, {VCC(), IMM(0), T1});  // the borrow in: the + 1 of -(P)
+        // limb k: P_k = low word of c y_k + the previous high word; r_k = x_k - (P_k ^ m) - borrow
+        auto limb = [&](int k, bool last) {
+            E(M_V_MAD_U64_U32, {MAD, DUMMY, C, Yr(k), k ? CARRY : IMM(0)});
+            if (k == 0 && !last) E(M_V_MOV, {V(R_CARRY + 1), IMM(0)});
+            if (!last) E(M_V_MOV, {V(R_CARRY), V(R_MAD + 1)});
+            E(M_V_XOR, {V(R_MAD), V(R_MAD), T1});
+            E(M_V_SUBB_CO, {Xr(k), VCC(), Rr(k), V(R_MAD), VCC()});
+        };
+        // all eight limbs demanded (the common site) runs without the per-limb tests
+        E(M_S_CMP_LT_U32, {KIND, IMM((128u + 7u) << 3)});
+        E(M_S_CBRANCH_SCC0, {LBL(L_SFULL)});
+        for (int k = 0; k < 7; ++k) {
+            limb(k, false);
+            E(M_S_CMP_LT_U32, {KIND, IMM((128u + (uint32_t)k + 1u) << 3)});
+            E(M_S_CBRANCH_SCC1, {LBL(L_WB)});
+        }
+        E(M_S_BRANCH, {LBL(L_WB)});  // not reached: top < 7 left the chain above
+        L(L_SFULL);
+        for (int k = 0; k < 8; ++k) limb(k, k == 7);
+        E(M_S_BRANCH, {LBL(L_WB)});
+        L(L_SCOLD);
+        for (int k = 0; k < 8; ++k) E(M_V_XOR, {Yr(k), Yr(k), SY});
+        E(M_V_SUB_CO, {Yr(0), VCC(), Yr(0), SY});
+        for (int k = 1; k < 8; ++k) E(M_V_SUBB_CO, {Yr(k), VCC(), Yr(k), SY, VCC()});
+        for (int k = 0; k < 8; ++k) E(M_V_XOR, {Rr(k), Rr(k), SX});
+        E(M_V_SUB_CO, {Rr(0), VCC(), Rr(0), SX});
+        for (int k = 1; k < 8; ++k) E(M_V_SUBB_CO, {Rr(k), VCC(), Rr(k), SX, VCC()});
+        E(M_S_MOV_B32, {KIND, IMM(3)});  // FLAG6 is as the site set it
+        E(M_S_BRANCH, {LBL(L_UNS)});
+    }
     return o;
 }
 
@@ -3815,11 +3991,12 @@ Module build_module(const std::vector<const TapeCode*>& codes,
     }
     const uint32_t n_pin = pinned_cols(n_vars);
     uint32_t maxv = R_COL0 + 8 * n_pin;
-    bool any_div = false, any_divw = false, any_lds = false, any_kec = false;
+    bool any_div = false, any_divw = false, any_dive = false, any_lds = false, any_kec = false;
     for (const TapeCode* tc : codes) {
         maxv = std::max(maxv, tc->max_vgpr);
         any_div |= tc->calls_div;
-        any_divw |= tc->calls_divw;
+        any_divw |= tc->calls_divw || tc->calls_dive;  // the width dispatch enters the variants
+        any_dive |= tc->calls_dive;
         any_lds |= tc->uses_lds;
         any_kec |= tc->calls_kec;
     }
@@ -4013,10 +4190,17 @@ Module build_module(const std::vector<const TapeCode*>& codes,
         // this module calls one: the other modules keep the text they had
         std::vector<MI> dv;
         bool keep = true;
+        // likewise the level-6 head, width dispatch and raw srem entry (labels 200..203, which
+        // are never printed themselves)
         for (const MI& mi : div_routine()) {
-            if (mi.op == M_LABEL && !any_divw) {
-                if (mi.o[0].v == 128 || mi.o[0].v == 129) keep = false;  // L_WHEAD, L_WSEC
-                else if (mi.o[0].v == 1) keep = true;                    // L_UNS
+            if (mi.op == M_LABEL) {
+                const uint32_t l = mi.o[0].v;
+                if (l == 128 || l == 129) keep = any_divw;               // L_WHEAD, L_WSEC
+                else if (l == 1) keep = true;                            // L_UNS
+                else if (l >= 200 && l <= 203) {                         // L_EHEAD .. L_BEND
+                    keep = l == 203 ? true : any_dive;
+                    continue;
+                }
             }
             if (keep) dv.push_back(mi);
         }
@@ -4396,10 +4580,11 @@ static std::atomic<uint64_t> g_sc_fallbacks{0};
 // Staged conjuncts (emit_staged): MH_JIT_STAGE = 0 off, 1 == conjuncts, 2 + ordered compares from
 // exact top limbs, 3 + add / sub with the carry-in left open, 4 + products from their two top
 // columns, 5 + the division subroutine's width-specialised variants (op_div; MH_JIT_DIV=0
-// switches them off with the other division layers).
+// switches them off with the other division layers), 6 + its raw srem entry and run-time width
+// dispatch (the same switch).
 static int stage_level() {
     const char* e = std::getenv("MH_JIT_STAGE");  // read per tape: tests switch it in-process
-    return e ? std::min(5, std::max(0, atoi(e))) : 5;
+    return e ? std::min(6, std::max(0, atoi(e))) : 6;
 }
 
 // Inline division fast paths (Emitter::op_div): MH_JIT_DIV = 0 off, 1 dividends known shorter
@@ -4410,6 +4595,14 @@ static int div_level() {
     if (s && atoi(s) <= 0) return 0;
     const char* e = std::getenv("MH_JIT_DIV");
     return e ? std::min(3, std::max(0, atoi(e))) : 3;
+}
+
+// Level 6's two layers, for pricing them apart (scripts/div_entry_stats.py): MH_JIT_ENTRY = 1 the
+// raw srem entry only (its site clears S_DIV_FLAG6, so its fallback into the legacy code is not
+// dispatched either), 2 the run-time width dispatch only, 3 (default) both.
+static int entry_layers() {
+    const char* e = std::getenv("MH_JIT_ENTRY");  // read per tape, like stage_level()
+    return e ? (atoi(e) & 3) : 3;
 }
 
 uint64_t sc_fallbacks(bool reset) {
@@ -4436,10 +4629,12 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
     // the division variants follow the build's level (MH_JIT_STAGE), not opt.stage: the parity
     // build (values, opt.stage = 0) and a tape kept at stage 3 for its registers call them too
     const bool divw = dlevel > 0 && stage_level() >= 5;
+    const int dive = dlevel > 0 && stage_level() >= 6 ? entry_layers() : 0;
     std::vector<double> cost;
     Emitter e(st, pool, n_vars, opt, nullptr, opt.short_circuit ? &cost : nullptr);
     e.div_ = opt.short_circuit ? 0 : dlevel;
     e.divw_ = !opt.short_circuit && divw;
+    e.dive_ = opt.short_circuit ? 0 : dive;
     TapeCode tc0 = e.run();
     if (opt.short_circuit) {
         SsaTape sc;
@@ -4453,6 +4648,7 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
                 e2.stage_ = level;
                 e2.div_ = dlevel;
                 e2.divw_ = divw;
+                e2.dive_ = dive;
                 TapeCode tc = e2.run();
                 if (tc.ok && !e2.stage_rejected_.empty()) {
                     std::vector<uint8_t> skip((size_t)sc.n_vregs, 0);
@@ -4461,6 +4657,7 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
                     e3.stage_ = level;
                     e3.div_ = dlevel;
                     e3.divw_ = divw;
+                    e3.dive_ = dive;
                     e3.stage_skip_ = &skip;
                     tc = e3.run();
                 }
@@ -4478,6 +4675,7 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
             Emitter e2(sc, pool, n_vars, opt, &check);
             e2.div_ = dlevel;
             e2.divw_ = divw;
+            e2.dive_ = dive;
             TapeCode tc = e2.run();
             if (tc.ok) return tc;  // else (register pressure of the new order): source order
             g_sc_fallbacks.fetch_add(1, std::memory_order_relaxed);
@@ -4486,6 +4684,7 @@ TapeCode emit_tape_body(const SsaTape& st, const std::vector<uint32_t>& pool, ui
             Emitter e4(st, pool, n_vars, opt);
             e4.div_ = dlevel;
             e4.divw_ = divw;
+            e4.dive_ = dive;
             TapeCode tc = e4.run();
             if (tc.ok) return tc;
         }

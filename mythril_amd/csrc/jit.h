@@ -122,7 +122,10 @@ enum : uint32_t {
     S_SCRATCH = 34,      // s[34:35]: scratch between tapes (short-circuit tests inside one)
     S_BOOL0 = 40, N_BOOL_PAIRS = 16,   // Bool lane masks s[40:71]
     S_KSTAGE = 72, N_KSTAGE = 4,       // constant staging s72..s75
-    S_DIV_RA = 76, S_DIV_TGT = 78, S_DIV_KIND = 80, S_DIV_YNZ = 82, S_DIV_DUMMY = 84,
+    S_DIV_RA = 76, S_DIV_TGT = 78, S_DIV_KIND = 80,
+    S_DIV_FLAG6 = 81,    // 1: the legacy code may hand a uniformly short divisor to its variant
+                         // (level-6 sites; written by the entry head or the raw srem site)
+    S_DIV_YNZ = 82, S_DIV_DUMMY = 84,
     S_DIV_MSK = 86, S_DIV_TM = 88, S_DIV_F64K = 90,
     S_PERM_SEL = 92,     // v_perm_b32 byte-swap selector
     S_NEXT_FREE = 93,
@@ -144,6 +147,8 @@ struct TapeCode {
     uint32_t max_vgpr = 0;      // highest VGPR used + 1
     bool calls_div = false;
     bool calls_divw = false;    // ... through a width-specialised variant (div_routine's marked part)
+    bool calls_dive = false;    // ... from a level-6 site (the entry head, the raw srem entry and
+                                // the run-time width dispatch: div_routine's other marked parts)
     bool uses_lds = false;      // variable shifts (the kernel then reserves LDS_WG_BYTES)
     bool calls_kec = false;
     bool root_bool = true;

@@ -684,6 +684,51 @@ int32_t mh_query_round_hits(mh_ctx* ctx, const mh_tapeset* ts, mh_assign* as, co
                             const mh_spares* spares /* NULL: none */, uint32_t k, uint64_t* hits,
                             uint32_t* n_hits, uint64_t* hit_count, uint32_t n_cols,
                             uint32_t* rows_out);
+/* Many independent listing rounds in one device submission: mh_query_round_many's shape with
+ * mh_query_round_hits' results.  Opt-in (Sieve(spares=K, batch_spares=True)); nothing else in the
+ * library calls it.
+ *
+ * Contract: for every job hits, n_hits, hit_count, rows_out and the contents of the job's
+ * mh_assign afterwards equal, bit for bit, what mh_query_round_hits writes with the same
+ * arguments.  Jobs may differ in k, count, n_cols, tape range and tape set, and some may carry
+ * spares and others none.  As both of those calls, the batch walks whole tapes with the
+ * interpreter, every (tape, row) Bool determined as in MH_MODE_COUNT_ALL: no native code, no
+ * split parts.
+ *
+ * One submission: one upload (the segments' parameters, the generator jobs, the block tables, the
+ * packed guides, one descriptor per job for the scatter / select / rows kernels and every job's
+ * spare cols and values); one guided-generator launch per generator form present; one scatter
+ * launch for all jobs' spares; one interpreter launch per register class present (spilled tapes in
+ * the spill class's), every segment writing wave masks into its job's slice of the ctx's hit masks;
+ * one select launch with a workgroup per (job, tape); one row-gather launch; one copy back and one
+ * sync.  The select and gather kernels run the single calls' code per job.
+ *
+ * Refusals, all before anything is queued or any device call is made: a refused batch leaves every
+ * buffer and every output untouched, and the message names the job ("mh_query_round_hits_many: job
+ * 3: ...").  The checks that read no handle come first: a null job list, n_jobs above
+ * MH_ROUND_MANY_MAX, k outside 1..MH_HITS_MAX, count == 0 (all MH_E_INVALID).  Then MH_E_INVALID:
+ * a null or foreign handle, a null guide, null hits / n_hits, two jobs sharing one mh_assign,
+ * n_cols beyond the buffer's columns, rows_out NULL with n_cols > 0, spares->n_rows > count, spare
+ * cols not strictly ascending or outside the buffer.  MH_E_UNSUPPORTED: count above 4096 or above
+ * the buffer's capacity, a tape set holding a lookup, a kernel variant the buffer's capacity does
+ * not fit, spill areas beyond the cap, or a result block (all jobs' lists, counts and rows) above
+ * MH_ROUND_HITS_MANY_MAX_BYTES -- it bounds the pinned memory of the copy back; callers chunk the
+ * list or fall back to one call per job.  n_jobs == 0 is MH_OK.  With mh_ctx_enable_timing the
+ * submission is one span.                                                                        */
+#define MH_ROUND_HITS_MANY_MAX_BYTES (64u << 20)
+typedef struct mh_round_hits_job {
+    const mh_tapeset* ts;
+    mh_assign* as;
+    const mh_guide* guide;
+    uint64_t seed, global_base, count;          /* count in 1..4096 */
+    uint32_t tape_first, tape_count, k, n_cols; /* k in 1..MH_HITS_MAX */
+    const mh_spares* spares;                    /* NULL: none; n_rows <= count */
+    uint64_t* hits;                             /* [tape_count][k] */
+    uint32_t* n_hits;                           /* [tape_count] */
+    uint64_t* hit_count;                        /* [tape_count] or NULL */
+    uint32_t* rows_out;                         /* [tape_count][k][n_cols][8]; NULL iff n_cols == 0 */
+} mh_round_hits_job;
+int32_t mh_query_round_hits_many(mh_ctx* ctx, const mh_round_hits_job* jobs, uint32_t n_jobs);
 
 /* ---- decision by enumeration (no reference counterpart; DESIGN.md §6 "Decision by enumeration") --
  * A group whose columns all have small provable domains is decided exactly: the device writes the

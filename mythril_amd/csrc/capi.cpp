@@ -2879,4 +2879,268 @@ int32_t mh_query_round_hits(mh_ctx* ctx, const mh_tapeset* ts, mh_assign* as, co
                        n_hits, hit_count, n_cols, rows_out);
 }
 
+int32_t mh_query_round_hits_many(mh_ctx* ctx, const mh_round_hits_job* jobs, uint32_t n_jobs) {
+    // everything below up to use_device() is host-only: a refused batch has queued nothing
+    const std::string who = "mh_query_round_hits_many: ";
+    if (!ctx) return set_err(MH_E_INVALID, who + "null ctx");
+    if (n_jobs == 0) return MH_OK;
+    if (n_jobs > MH_ROUND_MANY_MAX)
+        return set_err(MH_E_INVALID, who + std::to_string(n_jobs) +
+                                         " jobs, more than MH_ROUND_MANY_MAX (" +
+                                         std::to_string(MH_ROUND_MANY_MAX) + "): chunk the list");
+    if (!jobs) return set_err(MH_E_INVALID, who + "null job list");
+    const auto job_err = [&](uint32_t i, int32_t code, const std::string& what) {
+        return set_err(code, who + "job " + std::to_string(i) + ": " + what);
+    };
+    // k and the row count of every job come before any handle is read
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        const mh_round_hits_job& j = jobs[i];
+        if (j.k < 1 || j.k > MH_HITS_MAX)
+            return job_err(i, MH_E_INVALID, "k = " + std::to_string(j.k) +
+                                                " outside 1..MH_HITS_MAX");
+        if (j.count == 0)
+            return job_err(i, MH_E_INVALID, "count = 0 outside 1..MH_HITS_MAX_ROWS");
+    }
+    struct JobPlan {
+        GuideLayout L;
+        mh::Buckets::Range in[mh::kNumVariants];  // the job's tapes per bucket
+        size_t guide_off = 0, sp_off = 0;         // bytes of the device block
+        uint64_t mask_off = 0, mask_stride = 0;   // words of the ctx's hit masks
+        size_t o_hits = 0, o_count = 0, o_n = 0, o_rows = 0, rows_bytes = 0;  // result block
+    };
+    std::vector<JobPlan> jp(n_jobs);
+    std::vector<mh::batch::JobShape> shapes(n_jobs);
+    // the kernels' prefix tables: select | rows | scatter workgroups, n_jobs + 1 entries each
+    std::vector<uint32_t> prefix(3 * ((size_t)n_jobs + 1), 0);
+    uint32_t* const pre_sel = prefix.data();
+    uint32_t* const pre_rows = pre_sel + n_jobs + 1;
+    uint32_t* const pre_sc = pre_rows + n_jobs + 1;
+    size_t res_bytes = 0;
+    uint64_t mask_words = 0;
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        const mh_round_hits_job& j = jobs[i];
+        JobPlan& p = jp[i];
+        if (!j.ts || !j.as || !j.guide) return job_err(i, MH_E_INVALID, "null handle");
+        if (j.ts->ctx != ctx || j.as->ctx != ctx)
+            return job_err(i, MH_E_INVALID, "handles of another ctx");
+        if (!j.hits || !j.n_hits) return job_err(i, MH_E_INVALID, "null hits or n_hits");
+        for (uint32_t q = 0; q < i; ++q)
+            if (jobs[q].as == j.as)
+                return job_err(i, MH_E_INVALID, "shares its assignment buffer with job " +
+                                                    std::to_string(q));
+        if (j.count > mh::batch::kMaxRows)
+            return job_err(i, MH_E_UNSUPPORTED, std::to_string(j.count) + " rows, more than " +
+                                                    std::to_string(mh::batch::kMaxRows));
+        if (j.count > j.as->capacity)
+            return job_err(i, MH_E_UNSUPPORTED, std::to_string(j.count) +
+                                                    " rows, more than the buffer's capacity");
+        if (int32_t r = check_run_args(ctx, j.ts, j.tape_first, j.tape_count, j.as, 0, j.count,
+                                       MH_MODE_COUNT_ALL))
+            return job_err(i, r, g_err);
+        if (j.n_cols > j.as->n_vars)
+            return job_err(i, MH_E_INVALID, "n_cols beyond the buffer's columns");
+        if (j.n_cols && !j.rows_out)
+            return job_err(i, MH_E_INVALID, "rows_out null with n_cols > 0");
+        if (int32_t r = refuse_tables(j.ts)) return job_err(i, r, g_err);
+        uint32_t sp_rows = 0, sp_cols = 0;
+        if (j.spares) {
+            if (j.spares->n_rows > j.count)
+                return job_err(i, MH_E_INVALID, "spares->n_rows beyond count");
+            if (int32_t r = check_scatter_args(j.as, 0, j.spares->n_rows, j.spares->cols,
+                                               j.spares->n_cols, j.spares->values, "spares"))
+                return job_err(i, r, g_err);
+            if (j.spares->n_rows && j.spares->n_cols) {
+                sp_rows = j.spares->n_rows;
+                sp_cols = j.spares->n_cols;
+            }
+        }
+        if (int32_t r = check_guide(j.as, j.guide, &p.L)) return job_err(i, r, g_err);
+        // the job's tapes per interpreter bucket: whole tapes (ts->all), never split parts
+        mh::batch::JobShape& sh = shapes[i];
+        sh.count = j.count;
+        sh.whole = j.tape_first == 0 && j.tape_count == j.ts->n_tapes;
+        sh.gen_n_cols = p.L.nc;
+        sh.gen_span_words = (uint32_t)(p.L.o_eval - p.L.o_prob);
+        for (uint32_t v = 0; v < mh::kNumVariants; ++v) {
+            p.in[v] = j.ts->all.range(v, j.tape_first, j.tape_count);
+            sh.n_ids[v] = p.in[v].count;
+        }
+        // the job's slices of the masks and of the result block (mh_run_hits' layout per job)
+        const size_t tc = j.tape_count;
+        p.mask_stride = mh::sieve_mask_stride(j.count);
+        p.mask_off = mask_words;
+        mask_words += tc * p.mask_stride;
+        p.o_hits = res_bytes;
+        p.o_count = p.o_hits + tc * j.k * sizeof(uint64_t);
+        p.o_n = p.o_count + tc * sizeof(uint64_t);
+        p.o_rows = p.o_n + (tc * sizeof(uint32_t) + 7) / 8 * 8;
+        p.rows_bytes = tc * j.k * j.n_cols * 8 * sizeof(uint32_t);
+        res_bytes = p.o_rows + p.rows_bytes;
+        if (res_bytes > MH_ROUND_HITS_MANY_MAX_BYTES)
+            return job_err(i, MH_E_UNSUPPORTED,
+                           "the batch's lists and rows up to this job take " +
+                               std::to_string(res_bytes) +
+                               " bytes, more than MH_ROUND_HITS_MANY_MAX_BYTES (" +
+                               std::to_string(MH_ROUND_HITS_MANY_MAX_BYTES) +
+                               "): chunk the list or ask for fewer hits");
+        pre_sel[i + 1] = pre_sel[i] + j.tape_count;
+        pre_rows[i + 1] = pre_rows[i] + (j.n_cols ? j.tape_count * j.k : 0);
+        pre_sc[i + 1] = pre_sc[i] + mh::scatter_blocks(sp_rows, sp_cols);
+    }
+    const mh::batch::Plan plan = mh::batch::plan(shapes.data(), n_jobs);
+    // a launch's variant serves every segment in it: each must fit that segment's buffer
+    for (const auto& l : plan.launches)
+        for (uint32_t b = l.first; b < l.first + l.count; ++b) {
+            const uint32_t job = plan.segments[plan.blocks[b].seg].job;
+            if (!mh::variant_fits(l.variant, jobs[job].as->stride)) {
+                (void)refuse_capacity(jobs[job].as->stride);
+                return job_err(job, MH_E_UNSUPPORTED, g_err);
+            }
+        }
+    // the device block: segments' KParams | GenJob[] | HitsJob[] | prefix tables | block tables |
+    // guides | spares (cols, values per job)
+    const auto align = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_seg = 0;
+    const size_t o_gen = align(o_seg + plan.segments.size() * sizeof(mh::KParams));
+    const size_t o_hj = align(o_gen + n_jobs * sizeof(mh::GenJob));
+    const size_t o_pre = align(o_hj + n_jobs * sizeof(mh::HitsJob));
+    const size_t o_blk = align(o_pre + prefix.size() * sizeof(uint32_t));
+    const size_t o_gblk = align(o_blk + plan.blocks.size() * sizeof(mh::batch::BlockEntry));
+    size_t up_bytes = align(o_gblk + plan.gen_blocks.size() * sizeof(mh::batch::GenEntry));
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        jp[i].guide_off = up_bytes;
+        up_bytes = align(up_bytes + jp[i].L.words * sizeof(uint32_t));
+    }
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        jp[i].sp_off = up_bytes;
+        if (pre_sc[i + 1] != pre_sc[i]) {
+            const mh_spares& sp = *jobs[i].spares;
+            up_bytes = align(up_bytes +
+                             (sp.n_cols + (size_t)sp.n_rows * sp.n_cols * 8) * sizeof(uint32_t));
+        }
+    }
+    if (int32_t r = use_device(ctx)) return r;
+    if (int32_t r = ctx_batch_bufs(ctx, up_bytes)) return r;
+    // grow-only buffers: a call ends with a stream sync, so nothing queued uses the old blocks
+    MH_HIP(grow_buf(&ctx->d_hit_masks, &ctx->hit_masks_bytes,
+                    (size_t)std::max<uint64_t>(mask_words, 1) * sizeof(unsigned long long), 1 << 16,
+                    false));
+    void* dres_v = nullptr;
+    void* hres_v = nullptr;
+    MH_HIP(ctx_dbuf(ctx, std::max<size_t>(res_bytes, 8), &dres_v));
+    MH_HIP(ctx_hbuf(ctx, std::max<size_t>(res_bytes, 8), &hres_v));
+    char* const dres = static_cast<char*>(dres_v);
+    const char* const hres = static_cast<const char*>(hres_v);
+    char* const hb = static_cast<char*>(ctx->h_batch);
+    char* const db = static_cast<char*>(ctx->d_batch);
+    // fill the staging area
+    mh::GenJob* h_gen = reinterpret_cast<mh::GenJob*>(hb + o_gen);
+    mh::HitsJob* h_hj = reinterpret_cast<mh::HitsJob*>(hb + o_hj);
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        const mh_round_hits_job& j = jobs[i];
+        const JobPlan& p = jp[i];
+        pack_guide(j.guide, p.L, reinterpret_cast<uint32_t*>(hb + p.guide_off));
+        mh::GenJob g{};
+        g.assign = j.as->d;
+        g.stride = j.as->stride;
+        g.count = j.count;
+        g.seed = j.seed;
+        g.base = j.global_base;
+        g.g = guide_at(p.L, reinterpret_cast<const uint32_t*>(db + p.guide_off));
+        h_gen[i] = g;
+        mh::HitsJob h{};
+        h.masks = ctx->d_hit_masks + p.mask_off;
+        h.mask_stride = p.mask_stride;
+        h.index0 = j.global_base;
+        h.assign = j.as->d;
+        h.stride = j.as->stride;
+        h.o_hits = p.o_hits;
+        h.o_hit_count = p.o_count;
+        h.o_n_hits = p.o_n;
+        h.o_rows = p.o_rows;
+        h.row_count = (uint32_t)j.count;
+        h.k = j.k;
+        h.n_cols = j.n_cols;
+        if (pre_sc[i + 1] != pre_sc[i]) {
+            const mh_spares& sp = *j.spares;
+            uint32_t* w = reinterpret_cast<uint32_t*>(hb + p.sp_off);
+            std::memcpy(w, sp.cols, sp.n_cols * sizeof(uint32_t));
+            std::memcpy(w + sp.n_cols, sp.values,
+                        (size_t)sp.n_rows * sp.n_cols * 8 * sizeof(uint32_t));
+            h.sp_cols = reinterpret_cast<const uint32_t*>(db + p.sp_off);
+            h.sp_values = h.sp_cols + sp.n_cols;
+            h.sp_rows = sp.n_rows;
+            h.sp_n_cols = sp.n_cols;
+        }
+        h_hj[i] = h;
+    }
+    // every segment in masks mode, writing into its job's slice of the hit masks
+    mh::KParams* h_seg = reinterpret_cast<mh::KParams*>(hb + o_seg);
+    for (size_t si = 0; si < plan.segments.size(); ++si) {
+        const mh::batch::Segment& sg = plan.segments[si];
+        const mh_round_hits_job& j = jobs[sg.job];
+        mh::KParams p = make_params(j.ts, j.tape_first, j.as, 0, j.count, j.global_base,
+                                    MH_MODE_COUNT_ALL);
+        p.masks = ctx->d_hit_masks + jp[sg.job].mask_off;
+        p.mask_base = j.tape_first;
+        p.mask_stride = jp[sg.job].mask_stride;
+        p.tape_ids = j.ts->d_all + jp[sg.job].in[sg.first_bucket].first;
+        p.n_ids = sg.n_ids;
+        h_seg[si] = p;
+    }
+    if (int32_t r = batch_spill(ctx, plan, h_seg, [&](const mh::batch::Segment& sg) {
+            const mh_tapeset* ts = jobs[sg.job].ts;
+            return std::make_pair(ts, ts->all.ids.data() + jp[sg.job].in[sg.first_bucket].first);
+        }))
+        return r;
+    std::memcpy(hb + o_pre, prefix.data(), prefix.size() * sizeof(uint32_t));
+    if (!plan.blocks.empty())
+        std::memcpy(hb + o_blk, plan.blocks.data(),
+                    plan.blocks.size() * sizeof(mh::batch::BlockEntry));
+    if (!plan.gen_blocks.empty())
+        std::memcpy(hb + o_gblk, plan.gen_blocks.data(),
+                    plan.gen_blocks.size() * sizeof(mh::batch::GenEntry));
+    MH_HIP(span_begin(ctx));  // one span for the whole submission
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, s);
+    const mh::GenJob* d_gen = reinterpret_cast<const mh::GenJob*>(db + o_gen);
+    const mh::HitsJob* d_hj = reinterpret_cast<const mh::HitsJob*>(db + o_hj);
+    const uint32_t* d_pre = reinterpret_cast<const uint32_t*>(db + o_pre);
+    const mh::batch::GenEntry* d_gblk = reinterpret_cast<const mh::batch::GenEntry*>(db + o_gblk);
+    const mh::batch::BlockEntry* d_blk = reinterpret_cast<const mh::batch::BlockEntry*>(db + o_blk);
+    for (const auto& l : plan.gen_launches)
+        if (e == hipSuccess)
+            e = mh::launch_generate_guided_batch(d_gen, d_gblk + l.first, l.count, l.form,
+                                                 l.lds_bytes, s);
+    if (e == hipSuccess)
+        e = mh::launch_scatter_batch(d_hj, d_pre + 2 * ((size_t)n_jobs + 1), n_jobs,
+                                     pre_sc[n_jobs], s);
+    for (const auto& l : plan.launches)
+        if (e == hipSuccess)
+            e = mh::launch_sieve_batch(reinterpret_cast<const mh::KParams*>(db + o_seg),
+                                       d_blk + l.first, l.count, l.variant, s);
+    if (e == hipSuccess)
+        e = mh::launch_hits_select_batch(d_hj, d_pre, n_jobs, pre_sel[n_jobs], dres, s);
+    if (e == hipSuccess)
+        e = mh::launch_hits_rows_batch(d_hj, d_pre + n_jobs + 1, n_jobs, pre_rows[n_jobs], dres, s);
+    if (e == hipSuccess) e = span_end(ctx);
+    if (e == hipSuccess && res_bytes)
+        e = hipMemcpyAsync(hres_v, dres, res_bytes, hipMemcpyDeviceToHost, s);
+    // the staging area is read by the queued copy: wait even after an error
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return set_err(MH_E_DEVICE, who + hipGetErrorString(e));
+    for (uint32_t i = 0; i < n_jobs; ++i) {
+        const mh_round_hits_job& j = jobs[i];
+        const JobPlan& p = jp[i];
+        const size_t tc = j.tape_count;
+        if (!tc) continue;
+        std::memcpy(j.hits, hres + p.o_hits, tc * j.k * sizeof(uint64_t));
+        if (j.hit_count) std::memcpy(j.hit_count, hres + p.o_count, tc * sizeof(uint64_t));
+        std::memcpy(j.n_hits, hres + p.o_n, tc * sizeof(uint32_t));
+        if (j.n_cols) std::memcpy(j.rows_out, hres + p.o_rows, p.rows_bytes);
+    }
+    return MH_OK;
+}
+
 }  // extern "C"

@@ -5,6 +5,8 @@
 //                       as global indices; how many were listed; the tape's whole hit count
 //   hits_rows_kernel    the first n_cols columns of every listed row
 //   scatter_kernel      host-given values into chosen columns of a run of buffer rows
+// and their batched forms (mh_query_round_hits_many): the same bodies, a job's arguments out of a
+// device table, so a job's list cannot differ from the single call's.
 // Restated in tests/hits_ref.py.  Nothing here runs unless Sieve(spares > 0) or a caller of the
 // three entry points asks.
 #include <hip/hip_runtime.h>
@@ -26,16 +28,13 @@ constexpr u64 kNoHit = ~0ull;  // MH_NO_HIT
 // the slot of its first set bit, so the list is in row order whatever the scheduling.  Placing
 // stops once k slots are filled; the words after that are only counted.  Integer only.  Bits at or
 // past row_count in the last word are masked off here (nothing else pins them).
-__global__ void __launch_bounds__(kBlock)
-    hits_select_kernel(const unsigned long long* masks, u64 stride, u32 row_count, u64 index0, u32 k,
-                       u64* hits, u32* n_hits, u64* hit_count) {
+// (the body of both select kernels: m_t = the tape's mask words, out = its k list slots)
+__device__ __forceinline__ void select_tape(const unsigned long long* m_t, u32 row_count, u64 index0,
+                                            u32 k, u64* out, u32* n_hits_t, u64* hit_count_t) {
     __shared__ u32 s_wave[kWaves];
     __shared__ u32 s_run;    // hits in the words walked so far
     __shared__ u32 s_total;  // the tape's hits
     const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const u32 t = blockIdx.x;
-    const unsigned long long* m_t = masks + (u64)t * stride;
-    u64* out = hits + (u64)t * k;
     const u32 n_words = (row_count + 63u) >> 6;
     const u32 tail = row_count & 63u;
     if (tid == 0) {
@@ -88,18 +87,50 @@ __global__ void __launch_bounds__(kBlock)
     const u32 total = s_total, n = total < k ? total : k;
     for (u32 j = n + tid; j < k; j += kBlock) out[j] = kNoHit;
     if (tid == 0) {
-        n_hits[t] = n;
-        hit_count[t] = total;
+        *n_hits_t = n;
+        *hit_count_t = total;
     }
+}
+
+__global__ void __launch_bounds__(kBlock)
+    hits_select_kernel(const unsigned long long* masks, u64 stride, u32 row_count, u64 index0, u32 k,
+                       u64* hits, u32* n_hits, u64* hit_count) {
+    const u32 t = blockIdx.x;
+    select_tape(masks + (u64)t * stride, row_count, index0, k, hits + (u64)t * k, n_hits + t,
+                hit_count + t);
+}
+
+// The batched forms (mh_query_round_hits_many): the same bodies per job, the job's arguments read
+// from its HitsJob (kernels.h).  prefix[j] = the workgroups of the jobs before job j, prefix[n_jobs]
+// = the grid: a workgroup finds its job by bisection (a job may own none), at a wave-uniform
+// address, so the loads are scalar.
+__device__ __forceinline__ u32 job_of(const u32* prefix, u32 n_jobs, u32 b) {
+    u32 lo = 0, hi = n_jobs;
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (prefix[mid + 1] <= b) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;  // prefix[lo] <= b < prefix[lo + 1]
+}
+
+// one workgroup per (job, tape)
+__global__ void __launch_bounds__(kBlock)
+    hits_select_batch_kernel(const mh::HitsJob* jobs, const u32* prefix, u32 n_jobs, char* res) {
+    const u32 ji = job_of(prefix, n_jobs, blockIdx.x);
+    const mh::HitsJob j = jobs[ji];
+    const u32 t = blockIdx.x - prefix[ji];
+    select_tape(j.masks + (u64)t * j.mask_stride, j.row_count, j.index0, j.k,
+                reinterpret_cast<u64*>(res + j.o_hits) + (u64)t * j.k,
+                reinterpret_cast<u32*>(res + j.o_n_hits) + t,
+                reinterpret_cast<u64*>(res + j.o_hit_count) + t);
 }
 
 // one workgroup per (tape, slot): out[tape][slot][w] = column word w of the buffer row the slot
 // lists, zero for a slot without a hit (a row outside the buffer reads as none, as in
 // witness_rows_kernel)
-__global__ void __launch_bounds__(kBlock)
-    hits_rows_kernel(const u32* assign, u64 stride, const u64* hits, u64 index_base,
-                     u32 n_cols, u32* out) {
-    const u64 s = blockIdx.x;  // tape * k + slot
+__device__ __forceinline__ void rows_slot(const u32* assign, u64 stride, const u64* hits,
+                                          u64 index_base, u32 n_cols, u32* out, u64 s) {
     const u64 h = hits[s];
     const u64 row = h - index_base;
     const bool hit = h != kNoHit && h >= index_base && row < stride;
@@ -108,15 +139,45 @@ __global__ void __launch_bounds__(kBlock)
     for (u32 w = threadIdx.x; w < words; w += kBlock) o[w] = hit ? assign[(u64)w * stride + row] : 0u;
 }
 
+__global__ void __launch_bounds__(kBlock)
+    hits_rows_kernel(const u32* assign, u64 stride, const u64* hits, u64 index_base,
+                     u32 n_cols, u32* out) {
+    rows_slot(assign, stride, hits, index_base, n_cols, out, blockIdx.x);  // tape * k + slot
+}
+
+// one workgroup per (job, tape, slot) of the jobs that ask for rows
+__global__ void __launch_bounds__(kBlock)
+    hits_rows_batch_kernel(const mh::HitsJob* jobs, const u32* prefix, u32 n_jobs, char* res) {
+    const u32 ji = job_of(prefix, n_jobs, blockIdx.x);
+    const mh::HitsJob j = jobs[ji];
+    rows_slot(j.assign, j.stride, reinterpret_cast<const u64*>(res + j.o_hits), j.index0, j.n_cols,
+              reinterpret_cast<u32*>(res + j.o_rows), blockIdx.x - prefix[ji]);
+}
+
 // one thread per (column, limb, row), the row fastest: values[r][c][l] -> column cols[c], limb l of
 // buffer row first + r
-__global__ void __launch_bounds__(kBlock)
-    scatter_kernel(u32* assign, u64 stride, u64 first, u32 n_rows, const u32* cols, u32 n_cols,
-                   const u32* values) {
-    const u64 i = (u64)blockIdx.x * kBlock + threadIdx.x;
+__device__ __forceinline__ void scatter_word(u32* assign, u64 stride, u64 first, u32 n_rows,
+                                             const u32* cols, u32 n_cols, const u32* values,
+                                             u64 i) {
     if (i >= (u64)n_rows * n_cols * 8) return;
     const u32 r = (u32)(i % n_rows), cl = (u32)(i / n_rows), c = cl >> 3, l = cl & 7u;
     assign[((u64)cols[c] * 8 + l) * stride + first + r] = values[((u64)r * n_cols + c) * 8 + l];
+}
+
+__global__ void __launch_bounds__(kBlock)
+    scatter_kernel(u32* assign, u64 stride, u64 first, u32 n_rows, const u32* cols, u32 n_cols,
+                   const u32* values) {
+    scatter_word(assign, stride, first, n_rows, cols, n_cols, values,
+                 (u64)blockIdx.x * kBlock + threadIdx.x);
+}
+
+// every job's spares into rows [0, sp_rows) of its buffer: prefix counts kBlock-thread workgroups
+__global__ void __launch_bounds__(kBlock)
+    scatter_batch_kernel(const mh::HitsJob* jobs, const u32* prefix, u32 n_jobs) {
+    const u32 ji = job_of(prefix, n_jobs, blockIdx.x);
+    const mh::HitsJob j = jobs[ji];
+    scatter_word(j.assign, j.stride, 0, j.sp_rows, j.sp_cols, j.sp_n_cols, j.sp_values,
+                 (u64)(blockIdx.x - prefix[ji]) * kBlock + threadIdx.x);
 }
 
 }  // namespace
@@ -154,6 +215,34 @@ hipError_t launch_scatter(uint32_t* assign, uint64_t stride, uint64_t first, uin
     hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, assign,
                        stride, first, n_rows, cols, n_cols, values);
     return hipGetLastError();
+}
+
+hipError_t launch_hits_select_batch(const HitsJob* jobs, const uint32_t* prefix, uint32_t n_jobs,
+                                    uint32_t n_blocks, char* res, hipStream_t stream) {
+    if (n_blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(hits_select_batch_kernel, dim3(n_blocks), dim3(kBlock), 0, stream, jobs,
+                       prefix, n_jobs, res);
+    return hipGetLastError();
+}
+
+hipError_t launch_hits_rows_batch(const HitsJob* jobs, const uint32_t* prefix, uint32_t n_jobs,
+                                  uint32_t n_blocks, char* res, hipStream_t stream) {
+    if (n_blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(hits_rows_batch_kernel, dim3(n_blocks), dim3(kBlock), 0, stream, jobs, prefix,
+                       n_jobs, res);
+    return hipGetLastError();
+}
+
+hipError_t launch_scatter_batch(const HitsJob* jobs, const uint32_t* prefix, uint32_t n_jobs,
+                                uint32_t n_blocks, hipStream_t stream) {
+    if (n_blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(scatter_batch_kernel, dim3(n_blocks), dim3(kBlock), 0, stream, jobs, prefix,
+                       n_jobs);
+    return hipGetLastError();
+}
+
+uint32_t scatter_blocks(uint32_t n_rows, uint32_t n_cols) {
+    return (uint32_t)(((uint64_t)n_rows * n_cols * 8 + kBlock - 1) / kBlock);
 }
 
 }  // namespace mh

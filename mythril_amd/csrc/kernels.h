@@ -173,6 +173,31 @@ hipError_t launch_hits_rows(const uint32_t* assign, uint64_t stride, const uint6
 hipError_t launch_scatter(uint32_t* assign, uint64_t stride, uint64_t first, uint32_t n_rows,
                           const uint32_t* cols, uint32_t n_cols, const uint32_t* values,
                           hipStream_t stream);
+// One job of a batched listing round (mh_query_round_hits_many), on the device: what the three
+// launches above take, per job.  masks = the job's slice of the ctx's hit masks ([tc][mask_stride],
+// written by the job's masks-mode segments with mask_base = its first tape); o_* = byte offsets of
+// the job's hits [tc][k] u64 / hit_count [tc] u64 / n_hits [tc] u32 / rows [tc][k][n_cols][8] u32
+// in the batch's result block; sp_* = the job's spares in the uploaded block (sp_rows == 0: none).
+struct HitsJob {
+    const unsigned long long* masks;
+    uint64_t mask_stride, index0;  // index0 = global_base: the listing's and the rows' index base
+    uint32_t* assign;
+    uint64_t stride;
+    uint64_t o_hits, o_hit_count, o_n_hits, o_rows;
+    const uint32_t* sp_cols;
+    const uint32_t* sp_values;
+    uint32_t row_count, k, n_cols, sp_rows, sp_n_cols, pad;
+};
+// The batched forms: workgroup b belongs to the job j with prefix[j] <= b < prefix[j + 1] (device
+// tables of n_jobs + 1 entries; n_blocks = prefix[n_jobs]).  Select: a workgroup per (job, tape).
+// Rows: one per (job, tape, slot) of the jobs with n_cols > 0.  Scatter: scatter_blocks() per job.
+hipError_t launch_hits_select_batch(const HitsJob* jobs, const uint32_t* prefix, uint32_t n_jobs,
+                                    uint32_t n_blocks, char* res, hipStream_t stream);
+hipError_t launch_hits_rows_batch(const HitsJob* jobs, const uint32_t* prefix, uint32_t n_jobs,
+                                  uint32_t n_blocks, char* res, hipStream_t stream);
+hipError_t launch_scatter_batch(const HitsJob* jobs, const uint32_t* prefix, uint32_t n_jobs,
+                                uint32_t n_blocks, hipStream_t stream);
+uint32_t scatter_blocks(uint32_t n_rows, uint32_t n_cols);
 hipError_t launch_microbench(uint32_t kind, uint32_t iters, uint32_t blocks, uint32_t* sink,
                              hipStream_t stream);
 

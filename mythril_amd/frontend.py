@@ -88,7 +88,9 @@ def configure(*, fallback: Optional[Callable] = None, verify: Optional[Callable]
     Certifier, which keeps a path's compiled constraints between queries.
     ``decide`` (or SIEVE_DECIDE) says what a query the sieve decided UNSAT by enumeration becomes
     (decide_mode); the decisions themselves are switched on by the sieve option ``decide_rows``.
-    Sieve options (``rows``, ``spares``, ...) are further keywords, or one dict ``sieve_kwargs``."""
+    Sieve options (``rows``, ``spares``, ``batch_spares``, ...) are further keywords, or one dict
+    ``sieve_kwargs``; with ``spares`` and ``batch_spares`` the batched first rounds of ``prefetch``
+    try the ancestors' spare rows and store spares too."""
     if decide is not None:
         if decide not in (True, False, "audit"):
             raise ValueError("decide must be True, False or 'audit'")

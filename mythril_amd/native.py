@@ -160,6 +160,7 @@ SIGNATURES = {
     "mh_query_round_hits": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64,
                                         C.c_uint32, C.c_uint32, _vp, C.c_uint32, _u64p, _u32p,
                                         _u64p, C.c_uint32, _u32p]),
+    "mh_query_round_hits_many": (C.c_int32, [_vp, _vp, C.c_uint32]),
 }
 HITS_MAX = 64          # MH_HITS_MAX
 HITS_MAX_ROWS = 65536  # MH_HITS_MAX_ROWS
@@ -1267,6 +1268,56 @@ def query_round_many(ctx: Context, jobs: Sequence[dict]):
             res.append((fh, hc, rows, tc, n_cols))
         _check(ctx.lib.mh_query_round_many(ctx.h, arr, len(chunk)))
         out.extend((fh[:tc], hc[:tc], rows[:tc, :n_cols]) for fh, hc, rows, tc, n_cols in res)
+    return out
+
+
+class RoundHitsJob(C.Structure):
+    """mh_round_hits_job (include/mythril_hip.h)."""
+
+    _fields_ = [
+        ("ts", _vp), ("as_", _vp), ("guide", C.POINTER(Guide)),
+        ("seed", C.c_uint64), ("global_base", C.c_uint64), ("count", C.c_uint64),
+        ("tape_first", C.c_uint32), ("tape_count", C.c_uint32), ("k", C.c_uint32),
+        ("n_cols", C.c_uint32),
+        ("spares", C.POINTER(Spares)),
+        ("hits", _u64p), ("n_hits", _u32p), ("hit_count", _u64p), ("rows_out", _u32p),
+    ]
+
+
+ROUND_HITS_MANY_MAX_BYTES = 64 << 20  # MH_ROUND_HITS_MANY_MAX_BYTES
+
+
+def query_round_hits_many(ctx: Context, jobs: Sequence[dict]):
+    """Many listing rounds in one device submission (mh_query_round_hits_many).  Each job is a
+    dict of query_round_hits' arguments: tapes, assign, guide, seed, global_base, count, n_cols,
+    k and optionally spares, tape_first, tape_count.  Returns run_hits' tuple per job, each
+    equal to what query_round_hits returns for the job alone; lists beyond ROUND_MANY_MAX jobs
+    go up in chunks."""
+    out = []
+    for lo in range(0, len(jobs), ROUND_MANY_MAX):
+        chunk = jobs[lo:lo + ROUND_MANY_MAX]
+        arr = (RoundHitsJob * len(chunk))()
+        res, keep = [], []
+        for i, j in enumerate(chunk):
+            tapes, n_cols, k = j["tapes"], j["n_cols"], j["k"]
+            tf = j.get("tape_first", 0)
+            tc = j.get("tape_count")
+            tc = tapes.n_tapes - tf if tc is None else tc
+            hits, nh, hc, rows = _hits_out(tc, k, n_cols)
+            sp = None
+            if j.get("spares") is not None:
+                cols, values = _scatter_arrays(*j["spares"])
+                sp = Spares(values.shape[0], len(cols), _ptr(cols), _ptr(values))
+                keep.append((cols, values, sp))
+                sp = C.pointer(sp)
+            arr[i] = RoundHitsJob(tapes.h, j["assign"].h, C.pointer(j["guide"].guide), j["seed"],
+                                  j["global_base"], j["count"], tf, tc, k, n_cols, sp,
+                                  _ptr(hits, C.c_uint64), _ptr(nh), _ptr(hc, C.c_uint64),
+                                  _ptr(rows))
+            res.append((hits, nh, hc, rows, tc, n_cols))
+        _check(ctx.lib.mh_query_round_hits_many(ctx.h, arr, len(chunk)))
+        out.extend((hits[:tc], nh[:tc], hc[:tc], rows[:tc, :, :n_cols])
+                   for hits, nh, hc, rows, tc, n_cols in res)
     return out
 
 

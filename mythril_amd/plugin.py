@@ -203,7 +203,9 @@ class SievePlugin(LaserPlugin):
         self.installation = Installation()
         # prefetch=True (or SIEVE_PREFETCH=1; off by default): after every transaction the open
         # world states' constraints -- the queries the next round's filter is about to ask one
-        # by one (laser/ethereum/svm.py:201-203) -- are solved in one batch (frontend.prefetch)
+        # by one (laser/ethereum/svm.py:201-203) -- are solved in one batch (frontend.prefetch).
+        # The sieve options spares=K with batch_spares=True (SIEVE_SPARES / SIEVE_BATCH_SPARES)
+        # let that batch try the ancestors' spare rows and store spares for the states' children
         if prefetch is None:
             import os
 

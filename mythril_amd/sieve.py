@@ -479,7 +479,9 @@ def _row_values(row, columns: Sequence[str], cols: Sequence[int], out: Dict[str,
 class _Run:
     """One staged query's rounds in progress (Sieve._rounds): what the rounds, the repair step
     and the decision step read and fill.  ``first``: its first round's results when a batched
-    round has run it already (no round then lists spare hits)."""
+    round has run it already -- (first hits, witness rows, buffer, listing): without a listing
+    (None) no round of the query lists spare hits; with one (Sieve(batch_spares=True): the batch
+    listed them, (hits, n_hits, rows, the spare rows it tried first)) every round does."""
     __slots__ = ("sieve", "s", "first", "budget", "t0", "columns", "group_cols", "solved", "values",
                  "ghits", "first_index", "use_hits", "buffer")
 
@@ -489,7 +491,7 @@ class _Run:
         self.solved = [False] * len(self.group_cols)
         self.values: Dict[str, int] = {}
         # spare witnesses: a sequential query's guided rounds list K hits per group
-        self.use_hits = sieve.spares > 0 and first is None
+        self.use_hits = sieve.spares > 0 and (first is None or first[3] is not None)
         self.ghits: List[Optional[List[Dict[str, int]]]] = [None] * len(self.group_cols)
         self.first_index: Optional[int] = None  # the smallest over rounds, repair and decide
         self.buffer: Optional[native.Assignments] = None  # the sieve's, once a step needed it
@@ -551,7 +553,7 @@ class Sieve:
                  native_query: bool = True, second_round: Optional[str] = None,
                  keccak_second_chance: Optional[bool] = None, repair_rounds: int = 0,
                  repair_elites: Optional[int] = None, repair_children: Optional[int] = None,
-                 decide_rows: int = 0, spares: int = 0):
+                 decide_rows: int = 0, spares: int = 0, batch_spares: bool = False):
         self.ctx = native.Context(device)
         # host stages by the native query compiler (csrc/query.cpp); False: the Python stages
         # (lower.py, buckets, local_tapeset) it is checked against (tests/test_query_native.py)
@@ -621,6 +623,12 @@ class Sieve:
         # it.  SIEVE_SPARES overrides.
         self.spares = min(native.HITS_MAX, max(0, int(os.environ.get("SIEVE_SPARES", spares))))
         self.spare_witnesses: "OrderedDict[tuple, List[Dict[str, int]]]" = OrderedDict()
+        # spares in solve_many's batched first rounds: the batch lists K hits per group
+        # (native.query_round_hits_many) with every job's ancestor rows tried first, and the
+        # batched queries store spares, as solve() does.  Only with spares > 0; off by default: a
+        # batched first round then neither reads nor makes spares.  SIEVE_BATCH_SPARES overrides.
+        self.batch_spares = self.spares > 0 and os.environ.get(
+            "SIEVE_BATCH_SPARES", "1" if batch_spares else "0") == "1"
         # the last query this sieve missed after a device round, (key, schema): a model the
         # fallback then finds for it is learnt as its witness (learn)
         # (key, schema[, the keccak second chance's schema])
@@ -1088,7 +1096,9 @@ class Sieve:
                    budget_s: Optional[float] = None) -> List[Optional[Witness]]:
         """solve() for a list of independent queries of builder `b` (or of one builder per query,
         given as a list), with the first round of
-        every query that needs one run in one device submission (native.query_round_many)
+        every query that needs one run in one device submission (native.query_round_many; with
+        ``batch_spares`` native.query_round_hits_many, which lists every group's K smallest hits
+        after trying each query's ancestor rows first, as solve()'s first round does)
         instead of one submission each.  Returns a witness or None per query; ``last_many`` has,
         per query, ``miss`` (what last_miss would have been), ``rounds`` (last_rounds), ``unsat``
         (True for a query decided UNSAT, last_unsat; absent otherwise) and ``error`` (the exception
@@ -1106,6 +1116,7 @@ class Sieve:
         t0 = time.perf_counter()
         budget = self.budget_s if budget_s is None else min(self.budget_s, budget_s)
         n = len(queries)
+        packed: Dict[tuple, np.ndarray] = {}  # ancestors' rows as limbs, shared by siblings
         # (one builder for the list, or one per query: paths built in contexts of their own)
         bs = list(b) if isinstance(b, (list, tuple)) else [b] * n
         if len(bs) != n:
@@ -1160,13 +1171,21 @@ class Sieve:
                     for q in live:
                         s = staged[q]
                         n_cols = len(s.host.columns)
-                        jobs.append(dict(tapes=s.ct, assign=self._pool_buffer(n_cols, taken),
-                                         guide=s.guide, seed=self.seed, global_base=s.qno << 24,
-                                         count=self.first_rows, n_cols=n_cols,
-                                         mode=native.MODE_FIRST_HIT))
+                        job = dict(tapes=s.ct, assign=self._pool_buffer(n_cols, taken),
+                                   guide=s.guide, seed=self.seed, global_base=s.qno << 24,
+                                   count=self.first_rows, n_cols=n_cols)
+                        if self.batch_spares:
+                            # the rows the query's first round tries first: its ancestor has
+                            # finished (it is in an earlier batch), so they are what solve() reads
+                            job.update(k=self.spares, spares=self._spare_rows(
+                                s.key, s.parent, s.col_index, self.first_rows, packed))
+                        else:
+                            job["mode"] = native.MODE_FIRST_HIT
+                        jobs.append(job)
                     tb = time.perf_counter()
                     try:
-                        res = native.query_round_many(self.ctx, jobs)
+                        res = (native.query_round_hits_many(self.ctx, jobs) if self.batch_spares
+                               else native.query_round_many(self.ctx, jobs))
                     except native.SieveError:  # (a shape the batch refuses: one by one instead)
                         st.bump("batch_refused")
                         res = None
@@ -1174,8 +1193,13 @@ class Sieve:
                     if res is not None:
                         st.bump("batched_rounds", len(live))
                         st.bump("batches")
-                        for q, job, (fh, _, wrows) in zip(live, jobs, res):
-                            firsts[q] = (fh, wrows, job["assign"])
+                        for q, job, r in zip(live, jobs, res):
+                            if self.batch_spares:
+                                hh, nh, _, hrows = r
+                                firsts[q] = (hh[:, 0], hrows[:, 0], job["assign"],
+                                             (hh, nh, hrows, job["spares"]))
+                            else:
+                                firsts[q] = (r[0], r[2], job["assign"], None)
                 # 3. every query's later rounds and accounting, in list order
                 dup_of = dict(dups)
                 for q in range(i, j):
@@ -1249,11 +1273,13 @@ class Sieve:
                 return p
         return None
 
-    def _spare_rows(self, key: Optional[tuple], parent, col_index: Dict[str, int], n: int):
+    def _spare_rows(self, key: Optional[tuple], parent, col_index: Dict[str, int], n: int,
+                    packed: Optional[Dict[tuple, np.ndarray]] = None):
         """The rows a query's first round tries first: its ancestor's witness, then the ancestor's
         spares, over the columns every one of them and the query have -- (column numbers
         ascending, values u32 [rows, columns, 8]) -- or None when the ancestor has no spares.
-        At most `n` rows (the round's)."""
+        At most `n` rows (the round's).  ``packed`` (solve_many): the values by (ancestor key,
+        column names), so that siblings pack their ancestor's rows into limbs once."""
         pk = self._ancestor_key(key)
         extra = self.spare_witnesses.get(pk) if pk is not None else None
         if not extra or not parent or self.witnesses.get(pk) is not parent:
@@ -1263,10 +1289,15 @@ class Sieve:
         if not names:
             return None
         names.sort(key=col_index.__getitem__)
-        vals = np.zeros((len(rows), len(names), 8), dtype=np.uint32)
-        for i, r in enumerate(rows):
-            raw = b"".join((int(r[c]) & ((1 << 256) - 1)).to_bytes(32, "little") for c in names)
-            vals[i] = np.frombuffer(raw, dtype="<u4").reshape(len(names), 8)
+        vals = packed.get((pk, tuple(names), len(rows))) if packed is not None else None
+        if vals is None:
+            vals = np.zeros((len(rows), len(names), 8), dtype=np.uint32)
+            for i, r in enumerate(rows):
+                raw = b"".join((int(r[c]) & ((1 << 256) - 1)).to_bytes(32, "little")
+                               for c in names)
+                vals[i] = np.frombuffer(raw, dtype="<u4").reshape(len(names), 8)
+            if packed is not None:
+                packed[pk, tuple(names), len(rows)] = vals
         return np.array([col_index[c] for c in names], dtype=np.uint32), vals
 
     def _parent_kreads(self, b: TapeBuilder, schema: Schema, base_schema: Schema,
@@ -1409,6 +1440,12 @@ class Sieve:
         hrows, nh, n_sp = None, None, 0
         if rnd == 0 and run.first is not None:
             fh, wrows = run.first[0], run.first[1]  # run by solve_many's batched round
+            if run.first[3] is not None:  # which listed the hits and tried the ancestor's rows
+                _, nh, hrows, sp = run.first[3]
+                n_sp = len(sp[1]) if sp is not None else 0
+                st.bump("spare_rows", n_sp)
+                self.last_rounds["spares"] = n_sp
+                self.last_rounds["spare_hit"] = 0
         else:
             assign = run.assign()
             # generator, run, and the first witnesses with their rows' columns in one call and one
@@ -1452,8 +1489,8 @@ class Sieve:
     def _rounds(self, s: _Staged, budget: float, t0: float, first=None):
         """The rounds of a staged query: (witness or None, schema, whether a group left unsolved
         reads a keccak application).  ``first`` = (first_hit, witness rows, the buffer they were
-        generated into) of its first round when a batched round has run it already: the round
-        is then accounted and read as if it had run here."""
+        generated into, the listing or None: _Run) of its first round when a batched round has
+        run it already: the round is then accounted and read as if it had run here."""
         st, schema = self.stats, s.host.schema
         t_c = time.perf_counter()
         run = _Run(self, s, first, budget, t0)
@@ -1500,6 +1537,8 @@ class Sieve:
                     # leaves them in -- one deterministic launch on a rare path
                     run.assign().generate_guided(self.seed, s.guide.arrays(),
                                                  global_base=s.qno << 24, first=0, count=last_n)
+                    if first is not None and first[3] is not None and first[3][3] is not None:
+                        run.assign().scatter(0, *first[3][3])  # (with the rows it tried first)
                     st.bump("repair_regenerated")
                 self._repair(run, last_n, (s.qno << 24) + offset)
                 if all(run.solved):

@@ -19,6 +19,14 @@ every figure is the median over the kept runs with their min and max.
 
 One JSON line per (workload, order, setting), appended to out.jsonl when given.  --fake runs the
 policy on the CPU stand-in (tests/fake_hits.py; small rounds, no device times): a dry run.
+
+--batched measures spares in batched first rounds instead (Sieve(batch_spares=True)):
+the same two families in ``jumpi`` and ``bfs`` order through Sieve.solve_many, 8 and 64 queries
+per list, under three settings -- SIEVE_SPARES=0 (the baseline), K without batch_spares, K with it
+-- reporting per query the total / host / round milliseconds, recall, the spare-hit share and the
+queries asked; then the primitive: device and wall milliseconds of ``query_round_hits_many`` at k =
+K against ``query_round_many`` and against ``query_round_hits`` one by one, on the same 8 and 64
+jobs of 4096 rows.
 """
 import gc
 import json
@@ -179,15 +187,145 @@ def first_round(k, reps, warmup):
     return out
 
 
+def query_list(workload, order, n_paths, path_len):
+    """The family's queries in `order`, path after path: [(builder, root nodes)].  (In bfs order
+    no branch is dropped: the list does not depend on a setting's answers.)"""
+    out = []
+
+    def collect(ctx):
+        def ask(cs):
+            out.append((ctx.b, [c.node for c in cs]))
+            return True
+        return ask
+
+    if workload == "laser_like":
+        for ctx, cs in laser_paths():
+            ordered(cs, order, collect(ctx))
+    else:
+        for seed in range(n_paths):
+            ctx, cs, _, _ = planted_path("random", seed, path_len)
+            ordered(cs, order, collect(ctx))
+    return out
+
+
+SETTINGS = (("spares0", 0, False), ("spares", None, False), ("batch_spares", None, True))
+
+
+def run_many_once(qs, per, spares, batch_spares):
+    """The list through solve_many, `per` queries a call, on a fresh Sieve: (queries, answered,
+    spare hits, batched first rounds, total ms, host ms, round ms)."""
+    s = Sieve(spares=spares, batch_spares=batch_spares, **SIEVE_KW)
+    try:
+        gc.collect()
+        t0 = time.perf_counter()
+        for lo in range(0, len(qs), per):
+            part = qs[lo:lo + per]
+            s.solve_many([b for b, _ in part], [r for _, r in part],
+                         keys=[tuple(r) for _, r in part])
+        total = (time.perf_counter() - t0) * 1e3
+        st = s.stats
+        return (st.queries, st.hits, st.extra.get("spare_hits", 0),
+                st.extra.get("batched_rounds", 0), total, st.host_s * 1e3,
+                st.stage_s.get("run", 0.0) * 1e3)
+    finally:
+        s.close()
+
+
+def measure_many(k, workload, order, per, reps, warmup, n_paths, path_len):
+    qs = query_list(workload, order, n_paths, path_len)
+    recs = []
+    for name, spares, batch_spares in SETTINGS:
+        spares = k if spares is None else spares
+        runs = [run_many_once(qs, per, spares, batch_spares)
+                for _ in range(warmup + reps)][warmup:]
+        q = max(runs[0][0], 1)
+        recs.append({"batched": name, "workload": workload, "order": order, "per_list": per,
+                     "spares": spares, "batch_spares": batch_spares, "reps": reps,
+                     "warmup": warmup, "queries": runs[0][0], "answered": runs[0][1],
+                     "recall": round(runs[0][1] / q, 4), "spare_hits": runs[0][2],
+                     "spare_hit_share": round(runs[0][2] / q, 4), "batched_rounds": runs[0][3],
+                     "same_counts_every_run": all(r[:4] == runs[0][:4] for r in runs),
+                     "total_ms_per_query": _mmm([r[4] / q for r in runs]),
+                     "host_ms_per_query": _mmm([r[5] / q for r in runs]),
+                     "round_ms_per_query": _mmm([r[6] / q for r in runs])})
+    return recs
+
+
+def primitive(k, n_jobs, reps, warmup):
+    """The same n_jobs first rounds of 4096 rows (ether_thief's whole path, a buffer per job) by
+    query_round_many, by query_round_hits_many at k and by query_round_hits one by one."""
+    ctx, qs = queries()
+    cs = dict(qs)["ether_thief"]
+    s = Sieve(first_rows=4096)
+    bufs, out = [], []
+    try:
+        st = s._stage(ctx.b, [c.node for c in cs], None, False, 1)
+        n_cols, n = len(st.host.columns), s.first_rows
+        bufs = [s.ctx.assignments(s._col_capacity(n_cols), n) for _ in range(n_jobs)]
+        jobs = [dict(tapes=st.ct, assign=a, guide=st.guide, seed=s.seed, global_base=(i + 1) << 24,
+                     count=n, n_cols=n_cols, k=k, mode=native.MODE_FIRST_HIT)
+                for i, a in enumerate(bufs)]
+        calls = {
+            "query_round_many": lambda: native.query_round_many(s.ctx, jobs),
+            "query_round_hits_many": lambda: native.query_round_hits_many(s.ctx, jobs),
+            "query_round_hits_each": lambda: [native.query_round_hits(
+                s.ctx, st.ct, j["assign"], st.guide, s.seed, j["global_base"], n, n_cols, k)
+                for j in jobs]}
+        s.ctx.enable_timing(True)
+        for name, call in calls.items():
+            dev, wall = [], []
+            for i in range(warmup + reps):
+                s.ctx.kernel_time()
+                t0 = time.perf_counter()
+                call()
+                w = (time.perf_counter() - t0) * 1e3
+                ms, spans = s.ctx.kernel_time()
+                if i >= warmup:
+                    dev.append(ms)
+                    wall.append(w)
+            out.append({"primitive": name, "jobs": n_jobs, "k": None if name.endswith("_many")
+                        and "hits" not in name else k, "rows": n, "groups": st.ct.n_tapes,
+                        "columns": n_cols, "reps": reps, "warmup": warmup, "spans": spans,
+                        "device_ms": _mmm(dev), "wall_ms": _mmm(wall),
+                        "device_ms_per_job": _mmm([d / n_jobs for d in dev]),
+                        "wall_ms_per_job": _mmm([w / n_jobs for w in wall])})
+        s.ctx.enable_timing(False)
+        st.close()
+    finally:
+        for a in bufs:
+            a.close()
+        s.close()
+    return out
+
+
+def main_batched(path, k, reps, warmup, n_paths, path_len, fake):
+    recs = []
+    for workload in ("laser_like", "planted_random"):
+        for order in ("jumpi", "bfs"):
+            for per in (8, 64):
+                for r in measure_many(k, workload, order, per, reps, warmup, n_paths, path_len):
+                    recs.append(r)
+                    print(json.dumps(r), flush=True)
+    for n_jobs in ([] if fake else (8, 64)):
+        for r in primitive(k, n_jobs, max(reps, 20), warmup):
+            recs.append(r)
+            print(json.dumps(r), flush=True)
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "a") as f:
+            for r in recs:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     argv = [a for a in sys.argv[1:] if not a.startswith("--")]
     fake = "--fake" in sys.argv
     if fake:
         import pytest
 
-        from tests import fake_hits
+        from tests import fake_hits_many
 
-        fake_hits.install(pytest.MonkeyPatch())
+        fake_hits_many.install(pytest.MonkeyPatch())
         SIEVE_KW.update(rows=256, budget_s=60.0)
     path = argv[0] if argv else None
     k = int(argv[1]) if len(argv) > 1 else 16
@@ -196,6 +334,9 @@ def main():
     n_paths = int(argv[4]) if len(argv) > 4 else 20
     path_len = int(argv[5]) if len(argv) > 5 else 16
     os.environ.pop("SIEVE_SPARES", None)  # the settings compared are this script's
+    os.environ.pop("SIEVE_BATCH_SPARES", None)
+    if "--batched" in sys.argv:
+        return main_batched(path, k, reps, warmup, n_paths, path_len, fake)
     recs = []
     for workload, orders in (("laser_like", ("laser", "jumpi", "bfs")), ("planted_random",
                                                                          ("laser",))):
